@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: env steps/sec (whole node), humanoid_soccer, 4096 envs per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly --steps steps and prints the result line. --full adds
+the legs that take runs of their own: the other-precision line and the one-core CPU oracle baseline
+(`cpu_baseline`). --dump-outputs DIR writes what the last timed step returned to its caller (obs,
+reward, terminated, truncated) as DIR/<name>.npy; with the same arguments the actions and reset
+draws are the same from run to run, so two builds can be compared output for output.
 
 `--gpus N` alone (no WORLD_SIZE in the environment) starts the N rank processes itself, one per
 GPU, before any GPU call (spawn_ranks); under a launcher, --gpus must equal WORLD_SIZE.
@@ -114,6 +120,23 @@ def _finite(x: float):
     """JSON-safe mean: the bipedal approach term is +inf on the first step after a reset
     (rescue_env.py:632-635), which makes a rollout's reward sum infinite."""
     return round(x, 3) if np.isfinite(x) else None
+
+
+DUMP_NAMES = ("obs", "reward", "terminated", "truncated")
+
+
+def dump_outputs(directory: str, returned, world: int = 1, rank: int = 0, prefix: str = "") -> None:
+    """--dump-outputs: what one step() call returned (obs, reward, terminated, truncated, info)
+    as DIR/<prefix><name>.npy (with more than one rank, <name>.rank<r>.npy), floating arrays in
+    their own precision (float32 / float64), the uint8 flags as float32. Whole arrays: the largest
+    config (8192 envs x 102 obs) is under 4 MB."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in zip(DUMP_NAMES, returned):
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        sfx = f".rank{rank}" if world > 1 else ""
+        np.save(os.path.join(directory, f"{prefix}{name}{sfx}.npy"), a)
 
 
 def timed_region(step, steps: int, sync, dist=None) -> float:
@@ -427,12 +450,14 @@ def bench_mixed(args, dev, world, rank, dist):
         env.reset()
     torch.cuda.synchronize(dev)
 
+    last = {}  # per task, what its latest step() returned (--dump-outputs)
+
     def one_step(i, ev=None):
         for k, (env, _, _) in tasks.items():
             with torch.cuda.stream(streams[k]):
                 if ev is not None:
                     ev[k][0].record(streams[k])
-                env.step(pools[k][i % 8], stream=streams[k])
+                last[k] = env.step(pools[k][i % 8], stream=streams[k])
                 if ev is not None:
                     ev[k][1].record(streams[k])
     for i in range(args.warmup):
@@ -446,6 +471,9 @@ def bench_mixed(args, dev, world, rank, dist):
            for _ in range(args.steps)]
     elapsed = timed_region(lambda i: one_step(i, evs[i]), args.steps, lambda: torch.cuda.synchronize(dev), dist)
     per = {k: float(np.mean([e[k][0].elapsed_time(e[k][1]) for e in evs])) for k in tasks}
+    if args.dump_outputs:
+        for k in tasks:
+            dump_outputs(args.dump_outputs, last[k], world, rank, prefix=k + "_")
     acc = torch.zeros(6, dtype=torch.float64, device=dev)
     # per task, over the timed region: MuJoCo's bad-state auto-resets and the env steps whose
     # contacts / rows exceeded the task's capacity (0 when every row MuJoCo keeps was kept)
@@ -631,9 +659,15 @@ def main():
     # (qpos drift < 1e-4 over 1000 steps vs the fp64 oracle); fp32 rides along as an extra key
     ap.add_argument("--precision", default=None, choices=["f32", "f64"],
                     help="default: f64 (MuJoCo's mjtNum, the parity precision) for every task")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the other-precision line and the "
+                         "one-core CPU oracle baseline (off by default: a plain run only times --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, terminated, truncated) as "
+                         "DIR/<name>.npy (mixed: DIR/<task>_<name>.npy)")
     ap.add_argument("--cpu-envs", type=int, default=16)
     ap.add_argument("--cpu-steps", type=int, default=2000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--mono", action="store_true", help="monolithic one-wave-per-env kernel instead of the staged step")
     ap.add_argument("--banks", type=int, default=3, help="reset banks per env (3: measured fastest, DESIGN.md §4)")
     ap.add_argument("--full-capacity", action="store_true",
@@ -650,7 +684,7 @@ def main():
                          "on one stream (envs/sharded.py serial shards: one sub-batch's B live in the "
                          "Infinity Cache at a time)")
     ap.add_argument("--no-f64-line", "--no-other-line", dest="no_f64_line", action="store_true",
-                    help="skip the other-precision soccer line (fp32 when the headline is fp64)")
+                    help="with --full: skip the other-precision line (fp32 when the headline is fp64)")
     ap.add_argument("--mix-streams", type=int, default=4, help="mixed: 4 grouped streams (default) or 7 (one per task)")
     ap.add_argument("--mix-priority", type=int, default=1, help="mixed: construction's stream at high priority (1)")
     ap.add_argument("--mix-staged", type=int, default=1,
@@ -679,6 +713,8 @@ def main():
         args.mono = True  # one fused wave-per-env launch per step
     if args.precision is None:
         args.precision = "f64"
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
     if args.envs <= 0:
         args.envs = {"bipedal": 8192, "mixed": 1024, "assembly": 1024, "construction": 1024}.get(args.task, 4096)
 
@@ -746,12 +782,16 @@ def main():
     warn0 = sum(int(e.batch.warning.sum().item()) for e in shards)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
 
+    last = [None]  # what the latest step() returned (--dump-outputs)
+
     def one_step(k):
         ev[k][0].record()
-        env.step(pool[k % len(pool)])
+        last[0] = env.step(pool[k % len(pool)])
         ev[k][1].record()
     elapsed = timed_region(one_step, args.steps, lambda: torch.cuda.synchronize(dev), dist)
     launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], world, rank)
     ro = torch.cat([e.rollout for e in shards]).double().sum(0)
     acc[0] = ro[3]
     acc[1] = float(sum(int(e.episode.sum().item()) for e in shards) - ep0)
@@ -786,10 +826,10 @@ def main():
                                     if bmode == "staged" else "mgx_bipedal_step = k_bipedal<T,0,GB>"),
                          "alg_bytes_per_step": bytes_per_launch, "launch_ms": round(launch_ms, 4)},
         }
-        if not args.no_f64_line:
+        if args.full and not args.no_f64_line:
             other = "f32" if args.precision == "f64" else "f64"
             out[f"{other}_line"] = bipedal_other_line(args, dev, N, g, other)
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_bipedal(max(1, args.cpu_envs // 8), args.cpu_steps // 10)
         print(json.dumps(out))
     elif rank == 0 and args.task == "assembly":
@@ -813,7 +853,7 @@ def main():
                          "kernel": "mgx_assembly_step = k_assembly<T,0,GB>", "alg_bytes_per_step": bytes_per_launch,
                          "launch_ms": round(launch_ms, 4)},
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_assembly(2, max(5, args.cpu_steps // 2))
         print(json.dumps(out))
     elif rank == 0 and args.task == "construction":
@@ -867,7 +907,7 @@ def main():
                          "alg_bytes_per_step": bytes_per_launch,
                          "launch_ms": round(launch_ms, 4)},
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_parkour(max(1, args.cpu_envs // 4), args.cpu_steps // 4)
         print(json.dumps(out))
     elif rank == 0:
@@ -909,10 +949,10 @@ def main():
                                  "nefc_mean": round(fl["nefc_mean"], 2), "pgs_sweeps_mean": round(fl["pgs_sweeps_mean"], 2),
                                  "definition": "SURVEY 8(d) dense-equivalent: 2 nefc^2 nv (A) + 2 sweeps nefc^2 (PGS) "
                                                "+ 300 nbody, summed per env step in the kernel"}
-        if not args.no_f64_line and world == 1 and not args.mono and args.streams == 1:
+        if args.full and not args.no_f64_line and world == 1 and not args.mono and args.streams == 1:
             other = "f32" if args.precision == "f64" else "f64"
             out[f"{other}_line"] = other_precision_line(args, dev, N, g, other)
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_envs, args.cpu_steps)
         print(json.dumps(out))
     if dist:

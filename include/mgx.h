@@ -672,6 +672,62 @@ typedef struct mgx_construction_logic_io {
 int mgx_construction_logic_test(const mgx_model *m, const mgx_construction_logic_io *io,
                                 const mgx_construction_env *e, int n_env, void *stream);
 
+/* ---- ray casting and depth cameras (MuJoCo's mj_ray / mj_multiRay [ext]) ------------------ */
+/* A ray is p + x v, x >= 0; v need not be normalised and x is in units of |v|. The result is the
+ * smallest x at which the ray meets the surface of an enabled geom (a ray that starts inside a
+ * closed geom hits its exit surface), or dist = -1 / geomid = -1 for a miss. Planes are hit from
+ * the front only, inside their rectangle when size[0] / size[1] > 0 (0 = infinite).
+ * Rays see the geom poses of the CURRENT qpos (what mj_kinematics gives now), computed by
+ * mgx_ray_scene into a caller-owned scene buffer; they never read the stale pre-integration
+ * frames of mgx_frames. Models that hold an hfield, mesh or ellipsoid geom are refused by
+ * mgx_ray_configure with MGX_E_UNSUPPORTED (mgx_model_create is unchanged), and every later ray
+ * call on them returns MGX_E_UNSUPPORTED too. */
+#define MGX_CAM_FIXED 0     /* body frame o (cam_pos, cam_quat) */
+#define MGX_CAM_TRACK 1     /* xpos[body] + cam_pos0, orientation cam_mat0 */
+#define MGX_CAM_TRACKCOM 2  /* subtree_com[body] + cam_poscom0, orientation cam_mat0 */
+#define MGX_RAY_MAX_CAM 16
+
+/* Host tables (the Python MJCF compiler's Model.cam_* fields); copied by mgx_ray_configure. */
+typedef struct mgx_ray_desc {
+  int32_t ngeom, ncam;          /* ngeom must equal the model's; ncam <= MGX_RAY_MAX_CAM */
+  const uint8_t *geom_enable;   /* [ngeom] 0: eliminated by default (rgba alpha 0 and no material [ext]) */
+  const int32_t *cam_bodyid;    /* [ncam] */
+  const int32_t *cam_mode;      /* [ncam] MGX_CAM_* */
+  const double *cam_pos;        /* [ncam][3] in the body frame */
+  const double *cam_quat;       /* [ncam][4] in the body frame */
+  const double *cam_fovy;       /* [ncam] vertical field of view, degrees */
+  const double *cam_pos0;       /* [ncam][3] world offset from xpos[body] at qpos0 */
+  const double *cam_poscom0;    /* [ncam][3] world offset from subtree_com[body] at qpos0 */
+  const double *cam_mat0;       /* [ncam][9] world orientation at qpos0 */
+} mgx_ray_desc;
+
+int mgx_ray_configure(mgx_model *m, const mgx_ray_desc *desc);
+
+/* The scene of N envs: per env the geom world poses and every camera's world pose, in the
+ * model's real type. mgx_ray_scene runs kinematics from state->qpos (one wave per env; for
+ * trackcom cameras also the subtree COM of the camera's body) and writes every byte of a selected
+ * env's scene that a later call reads. env_mask (uint8 [N], nullable) selects envs. */
+int64_t mgx_ray_scene_bytes(const mgx_model *m, int n_env);
+int mgx_ray_scene(const mgx_model *m, const mgx_state *state, void *scene, uint64_t bytes, int n_env,
+                  const uint8_t *env_mask, void *stream);
+
+/* n_ray rays per env: pnt, vec [N][n_ray][3] and dist [N][n_ray] in the model's real type, geomid
+ * [N][n_ray] int32. Enabled geoms: enabled by default AND geom_enable[g] != 0 (device uint8
+ * [ngeom], nullable) AND geom_bodyid[g] != bodyexclude (-1: none). Outputs of envs that env_mask
+ * deselects are left untouched. */
+int mgx_ray_cast(const mgx_model *m, const void *scene, const void *pnt, const void *vec, int n_ray,
+                 const uint8_t *geom_enable, int bodyexclude, void *dist, int32_t *geomid, int n_env,
+                 const uint8_t *env_mask, void *stream);
+
+/* Depth image of camera `cam` for every env; the rays are generated in the kernel. The camera
+ * looks along its -Z, +X right, +Y up; pixel (r, c) of height x width (row 0 at the top) casts
+ * v = R_cam ((2 (c + 1/2) / W - 1) t W / H, (1 - 2 (r + 1/2) / H) t, -1), t = tan(fovy / 2), so
+ * the distance is the planar (z-) depth. depth float32 [N][H][W] (+inf for a miss, nullable), seg
+ * int32 [N][H][W] (geom id or -1, nullable). */
+int mgx_ray_camera(const mgx_model *m, const void *scene, int cam, int height, int width,
+                   const uint8_t *geom_enable, int bodyexclude, float *depth, int32_t *seg, int n_env,
+                   const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

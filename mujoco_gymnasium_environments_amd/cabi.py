@@ -224,6 +224,45 @@ class MgxSoccerIds(C.Structure):
                 ("robot_geom_mask_lo", C.c_uint64), ("robot_geom_mask_hi", C.c_uint64)]
 
 
+MGX_CAM_FIXED, MGX_CAM_TRACK, MGX_CAM_TRACKCOM = 0, 1, 2  # include/mgx.h camera modes
+MGX_RAY_MAX_CAM = 16
+
+
+class MgxRayDesc(C.Structure):
+    _fields_ = [("ngeom", C.c_int32), ("ncam", C.c_int32), ("geom_enable", C.POINTER(C.c_uint8)),
+                ("cam_bodyid", P_I32), ("cam_mode", P_I32), ("cam_pos", P_F64), ("cam_quat", P_F64),
+                ("cam_fovy", P_F64), ("cam_pos0", P_F64), ("cam_poscom0", P_F64), ("cam_mat0", P_F64)]
+
+
+def ray_default_enable(model: Model) -> np.ndarray:
+    """uint8 [ngeom]: 0 for the geoms ray casting eliminates by default, as mj_ray does: rgba alpha
+    exactly 0 and no material."""
+    alpha = np.asarray(model.geom_rgba).reshape(-1, 4)[:, 3]
+    has_mat = np.array([bool(n) for n in model.geom_material], dtype=bool)
+    return np.ascontiguousarray(~((alpha == 0) & ~has_mat), dtype=np.uint8)
+
+
+class PackedRay:
+    """Holds an ``MgxRayDesc`` (mgx_ray_configure) plus the numpy arrays it points to."""
+
+    def __init__(self, model: Model):
+        A = model.arrays
+        self.arrays = {"geom_enable": ray_default_enable(model)}
+        d = MgxRayDesc()
+        d.ngeom, d.ncam = int(model.ngeom), len(model.cam_names)
+        if self.arrays["geom_enable"].size == 0:
+            self.arrays["geom_enable"] = np.zeros(1, np.uint8)
+        d.geom_enable = self.arrays["geom_enable"].ctypes.data_as(C.POINTER(C.c_uint8))
+        for name, kind in (("cam_bodyid", "i"), ("cam_mode", "i"), ("cam_pos", "d"), ("cam_quat", "d"),
+                           ("cam_fovy", "d"), ("cam_pos0", "d"), ("cam_poscom0", "d"), ("cam_mat0", "d")):
+            arr = np.ascontiguousarray(A[name], dtype=_NP[kind]).reshape(-1)
+            if arr.size == 0:
+                arr = np.zeros(1, dtype=_NP[kind])
+            self.arrays[name] = arr
+            setattr(d, name, arr.ctypes.data_as(_PTR[kind]))
+        self.desc = d
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

@@ -978,6 +978,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
 
 int mgx_model_destroy(mgx_model* m) {
   if (!m) return MGX_OK;
+  mgx::ray_release(m);
   if (m->dbuf) (void)hipFree(m->dbuf);
   delete m;
   return MGX_OK;

@@ -37,6 +37,7 @@ struct Hooks {
   int rows_lds = 0;      // MGX_ROWS_LDS: pad the row builder's LDS (occupancy probe)
 };
 Hooks read_hooks();
+struct RayState;  // ray casting tables (mgx_ray.h), owned by the model once mgx_ray_configure ran
 }  // namespace mgx
 
 struct mgx_model {
@@ -68,6 +69,7 @@ struct mgx_model {
   bool wide = false;       // nv > 64: only the wide kernels (mgx_wide.h) run this model
   bool staged_ok = false;  // the staged soccer pipeline supports this model's capacities
   bool staged_rk_ok = false;  // the staged RK4 pipeline (bipedal) supports this model
+  mgx::RayState* ray = nullptr;  // mgx_ray_configure (mgx_ray.hip); freed by ray_release
 };
 
 namespace mgx {
@@ -149,6 +151,8 @@ int parkour_reset_staged(const mgx_model* m, const mgx_state* s, const mgx_parko
 int64_t parkour_workspace_bytes(const mgx_model* m, int n_env, int banks);
 int parkour_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks, hipStream_t st);
 int pgs_lanes();
+// ray casting (mgx_ray.hip): frees the model's ray tables (mgx_model_destroy)
+void ray_release(mgx_model* m);
 }  // namespace mgx
 
 #define MGX_WIDE_MSG "nv > 64: this model runs on the wide (two dofs per lane) kernels only"

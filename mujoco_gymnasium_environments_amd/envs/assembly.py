@@ -34,6 +34,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
+from ..rays import RayForwarding
 from ..spaces import Box, EnvBase, policy_action
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets",
@@ -140,7 +141,7 @@ class AssemblyTables:
         return s
 
 
-class AssemblyVectorEnv:
+class AssemblyVectorEnv(RayForwarding):
     """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

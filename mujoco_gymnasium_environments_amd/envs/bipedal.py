@@ -30,6 +30,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
+from ..rays import RayForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 
@@ -107,7 +108,7 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv:
+class BipedalVectorEnv(RayForwarding):
     """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

@@ -30,6 +30,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
+from ..rays import RayForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 
@@ -111,7 +112,7 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv:
+class DancingVectorEnv(RayForwarding):
     """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

@@ -23,6 +23,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
+from ..rays import RayForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 from .sharded import StreamShardedEnv
@@ -112,7 +113,7 @@ class ParkourTables:
         return np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.0, 1.0)])
 
 
-class ParkourVectorEnv:
+class ParkourVectorEnv(RayForwarding):
     """``num_envs`` quadruped_parkour envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 100}

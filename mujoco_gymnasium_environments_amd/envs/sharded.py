@@ -118,6 +118,28 @@ class StreamShardedEnv:
         self._fan_out(stream, lambda a, b, s, st: s.step(actions[a:b], stream=st))
         return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
+    @property
+    def cameras(self):
+        return self.shards[0].cameras
+
+    def render_depth(self, camera, height: int, width: int, segmentation: bool = True,
+                     bodyexclude: Optional[int] = None, mask: Optional[torch.Tensor] = None, stream=None):
+        """PhysicsBatch.render_depth over every shard: each shard's rows go into slices of one
+        [N, H, W] depth (and segmentation) tensor, cached per (H, W). Everything is launched on the
+        caller's stream: after step() that stream is already ordered after every shard (_fan_out),
+        so no side-stream work is needed."""
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        key = (int(height), int(width))
+        cache = self.__dict__.setdefault("_depth_out", {})
+        if key not in cache:
+            cache[key] = (torch.empty((self.num_envs,) + key, dtype=torch.float32, device=self.device),
+                          torch.empty((self.num_envs,) + key, dtype=torch.int32, device=self.device))
+        depth, seg = cache[key]
+        for (a, b), s in zip(self.bounds, self.shards):
+            s.batch.render_depth(camera, height, width, segmentation=segmentation, bodyexclude=bodyexclude,
+                                 mask=None if mask is None else mask[a:b], stream=cs, out=(depth[a:b], seg[a:b]))
+        return depth, (seg if segmentation else None)
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

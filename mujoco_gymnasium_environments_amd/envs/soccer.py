@@ -22,6 +22,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
+from ..rays import RayForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase
 from .sharded import StreamShardedEnv
@@ -127,7 +128,7 @@ class SoccerTables:
         return out
 
 
-class SoccerVectorEnv:
+class SoccerVectorEnv(RayForwarding):
     """``num_envs`` humanoid_soccer envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

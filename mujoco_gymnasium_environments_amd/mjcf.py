@@ -42,6 +42,8 @@ JNT_TYPES = {"free": 0, "ball": 1, "slide": 2, "hinge": 3}
 SOLVERS = {"pgs": 0, "cg": 1, "newton": 2}
 INTEGRATORS = {"euler": 0, "rk4": 1, "implicit": 2, "implicitfast": 3}
 CONES = {"pyramidal": 0, "elliptic": 1}
+CAM_FIXED, CAM_TRACK, CAM_TRACKCOM = 0, 1, 2   # mjtCamLight; include/mgx.h MGX_CAM_*
+CAM_MODES = {"fixed": 0, "track": 1, "trackcom": 2, "targetbody": 3, "targetbodycom": 4}
 MINVAL = 1e-15
 
 
@@ -187,6 +189,8 @@ class Model:
     geom_names: List[str] = field(default_factory=list)
     actuator_names: List[str] = field(default_factory=list)
     site_names: List[str] = field(default_factory=list)
+    cam_names: List[str] = field(default_factory=list)
+    geom_material: List[str] = field(default_factory=list)   # material name per geom ("" = none)
     arrays: Dict[str, np.ndarray] = field(default_factory=dict)
 
     def __getattr__(self, k):
@@ -334,6 +338,7 @@ class _Compiler:
         joints: List[dict] = []
         geoms: List[dict] = []
         sites: List[dict] = []
+        cams: List[dict] = []
 
         def walk(elem: ET.Element, parent: int, cls: str):
             bid = len(bodies)
@@ -401,7 +406,9 @@ class _Compiler:
                              solimp=_floats(ga.get("solimp"), 5, [0.9, 0.95, 0.001, 0.5, 2.0]),
                              density=float(ga.get("density", 1000.0)),
                              mass=float(ga["mass"]) if "mass" in ga else None,
-                             group=int(ga.get("group", 0)))
+                             group=int(ga.get("group", 0)),
+                             rgba=_floats(ga.get("rgba"), 4, [0.5, 0.5, 0.5, 1.0]),
+                             material=ga.get("material", ""))
                     fr = _floats(ga.get("friction"), None, [1, 0.005, 0.0001])
                     if fr.size < 3:   # partial friction spec keeps the remaining defaults
                         fr = np.concatenate([fr, np.array([1, 0.005, 0.0001])[fr.size:]])
@@ -413,6 +420,15 @@ class _Compiler:
                     sa = self._attrs(ch, childcls, "site")
                     sites.append(dict(name=sa.get("name", ""), body=bid,
                                       pos=_floats(sa.get("pos"), 3, [0, 0, 0]), quat=self._orient(sa)))
+                elif ch.tag == "camera":
+                    ca = self._attrs(ch, childcls, "camera")
+                    mode = ca.get("mode", "fixed")
+                    if mode not in CAM_MODES:
+                        raise ValueError(f"camera {ca.get('name', '')!r}: unknown mode {mode!r}")
+                    # fovy is in degrees whatever the compiler's angle unit
+                    cams.append(dict(name=ca.get("name", ""), body=bid, mode=CAM_MODES[mode],
+                                     pos=_floats(ca.get("pos"), 3, [0, 0, 0]), quat=self._orient(ca),
+                                     fovy=float(ca.get("fovy", 45.0))))
                 elif ch.tag == "inertial":
                     ia = dict(ch.attrib)
                     inr = dict(pos=_floats(ia.get("pos"), 3, [0, 0, 0]), quat=self._orient(ia),
@@ -711,6 +727,13 @@ class _Compiler:
             site_bodyid=np.array([s["body"] for s in sites], np.int32),
             site_pos=np.array([s["pos"] for s in sites]).reshape(-1, 3),
             site_quat=np.array([s["quat"] for s in sites]).reshape(-1, 4),
+            geom_group=np.array([g["group"] for g in geoms], np.int32),
+            geom_rgba=np.array([g["rgba"] for g in geoms]).reshape(-1, 4),
+            cam_bodyid=np.array([c["body"] for c in cams], np.int32),
+            cam_mode=np.array([c["mode"] for c in cams], np.int32),
+            cam_pos=np.array([c["pos"] for c in cams]).reshape(-1, 3),
+            cam_quat=np.array([c["quat"] for c in cams]).reshape(-1, 4),
+            cam_fovy=np.array([c["fovy"] for c in cams], np.float64),
         ))
         A.update(pairs)
         m.body_names = [b["name"] for b in bodies]
@@ -718,6 +741,8 @@ class _Compiler:
         m.geom_names = [g["name"] for g in geoms]
         m.actuator_names = [a["name"] for a in acts]
         m.site_names = [s["name"] for s in sites]
+        m.cam_names = [c["name"] for c in cams]
+        m.geom_material = [g["material"] for g in geoms]
         _set_const(m)
         return m
 
@@ -951,6 +976,16 @@ def _set_const(m: Model) -> None:
             diw[a] = Minv[a, a]
     A["body_invweight0"] = biw
     A["dof_invweight0"] = diw
+    # cameras at qpos0 (mj_setConst): world-frame offsets from the body origin and from its subtree
+    # com, and the world orientation, which the track / trackcom modes keep (mj_camlight)
+    nc = len(A["cam_bodyid"])
+    A["cam_pos0"], A["cam_poscom0"], A["cam_mat0"] = np.zeros((nc, 3)), np.zeros((nc, 3)), np.zeros((nc, 9))
+    for c in range(nc):
+        b = A["cam_bodyid"][c]
+        cx = xmat[b] @ A["cam_pos"][c] + xpos[b]
+        A["cam_pos0"][c] = cx - xpos[b]
+        A["cam_poscom0"][c] = cx - sc[b]
+        A["cam_mat0"][c] = quat2mat(quat_mul(xquat[b], A["cam_quat"][c])).reshape(-1)
 
 
 def compile_xml(xml: str, name: str = "") -> Model:

@@ -19,12 +19,13 @@ LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(PKG, "libmgx.so")
 CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
            "mgx_dancing.hip",
-           "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip"]
+           "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
 HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mgx_staged.h", "mgx_parkour.h",
-           "mgx_bipedal.h", "mgx_dancing.h", "mgx_martial.h", "mgx_internal.h", "mgx_wide.h", "mgx_construction.h"]
+           "mgx_bipedal.h", "mgx_dancing.h", "mgx_martial.h", "mgx_internal.h", "mgx_wide.h", "mgx_construction.h",
+           "mgx_ray.h"]
 # task headers included by one translation unit only (so editing one rebuilds one object)
 TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"]}
 
@@ -34,7 +35,7 @@ MGX_F64 = 1
 
 
 class NativeError(RuntimeError):
-    pass
+    code = None  # the library's MGX_E_* return code, when the error came from a call (check)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -171,6 +172,11 @@ _SIGS = {
                            C.c_int),
     "mgx_assembly_logic_test": ([_VP, C.POINTER(cabi.MgxAssemblyLogicIO), C.POINTER(cabi.MgxAssemblyEnv), C.c_int,
                                  _VP], C.c_int),
+    "mgx_ray_configure": ([_VP, C.POINTER(cabi.MgxRayDesc)], C.c_int),
+    "mgx_ray_scene_bytes": ([_VP, C.c_int], C.c_int64),
+    "mgx_ray_scene": ([_VP, C.POINTER(cabi.MgxState), _VP, C.c_uint64, C.c_int, _VP, _VP], C.c_int),
+    "mgx_ray_cast": ([_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
+    "mgx_ray_camera": ([_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -196,4 +202,6 @@ def lib() -> C.CDLL:
 def check(rc: int, what: str = "") -> None:
     if rc < 0:
         msg = lib().mgx_last_error().decode(errors="replace")
-        raise NativeError(f"{what} failed ({rc}): {msg}")
+        err = NativeError(f"{what} failed ({rc}): {msg}")
+        err.code = rc
+        raise err

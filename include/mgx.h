@@ -728,6 +728,97 @@ int mgx_ray_camera(const mgx_model *m, const void *scene, int cam, int height, i
                    const uint8_t *geom_enable, int bodyexclude, float *depth, int32_t *seg, int n_env,
                    const uint8_t *env_mask, void *stream);
 
+/* ---- sensors, mj_forward and contact forces (MuJoCo's mj_forward / mj_contactForce /
+ * data.sensordata [ext]) ------------------------------------------------------------------- */
+/* Everything here is computed at the CURRENT state (qpos, qvel, ctrl, applied forces), as after
+ * mj_forward(model, data): not the pre-integration values an mj_step leaves in data.sensordata.
+ * No call writes to mgx_state (no qacc_warmstart, time or warning), allocates or synchronises
+ * (mgx_sensor_configure excepted: it is a *_configure). */
+
+/* Sensor types: the index of the MJCF element in the library's list, mgx_sensor_type_name(code)
+ * (NULL past its end). The first MGX_SENS_NTYPE are computed; any other type still configures a
+ * model's physics but is refused by mgx_sensor_configure with MGX_E_UNSUPPORTED, named in the
+ * message. */
+#define MGX_SENS_JOINTPOS 0       /* 1: qpos of a hinge / slide joint */
+#define MGX_SENS_JOINTVEL 1       /* 1: qvel of a hinge / slide joint */
+#define MGX_SENS_FRAMEPOS 2       /* 3: world position of the object */
+#define MGX_SENS_FRAMEQUAT 3      /* 4: world orientation of the object */
+#define MGX_SENS_FRAMELINVEL 4    /* 3: world-frame linear velocity of the object's origin */
+#define MGX_SENS_FRAMEANGVEL 5    /* 3: world-frame angular velocity */
+#define MGX_SENS_GYRO 6           /* 3: angular velocity in the site frame */
+#define MGX_SENS_VELOCIMETER 7    /* 3: linear velocity of the site in the site frame */
+#define MGX_SENS_MAGNETOMETER 8   /* 3: option.magnetic in the site frame */
+#define MGX_SENS_ACCELEROMETER 9  /* 3: site acceleration minus gravity, site frame (+g on z at rest) */
+#define MGX_SENS_FORCE 10         /* 3: force the site's body subtree exchanges with its parent, site frame */
+#define MGX_SENS_TORQUE 11        /* 3: the torque of the same interaction, about the site */
+#define MGX_SENS_TOUCH 12         /* 1: sum of normal forces of the contacts inside the site's shape */
+#define MGX_SENS_NTYPE 13
+const char *mgx_sensor_type_name(int code);
+
+/* Objects a sensor may refer to (sensor_objtype). BODY is the inertial frame (xipos, ximat,
+ * xquat o body_iquat), XBODY the body frame. Anything else (camera ...) is refused. */
+#define MGX_OBJ_BODY 0
+#define MGX_OBJ_XBODY 1
+#define MGX_OBJ_JOINT 2
+#define MGX_OBJ_GEOM 3
+#define MGX_OBJ_SITE 4
+
+/* Host tables (the Python MJCF compiler's Model.site_* / sensor_* fields and option.magnetic);
+ * copied to the device once by mgx_sensor_configure. Sensors are in document order; sensor i owns
+ * sensordata[sensor_adr[i] .. + sensor_dim[i]). A sensor with sensor_reftype[i] >= 0 (a reftype /
+ * refname attribute) is refused like an unknown type. cutoff > 0 clamps real-valued sensors to
+ * +-cutoff and touch to [0, cutoff]; quaternions are never clamped. Noise is not simulated. */
+typedef struct mgx_sensor_desc {
+  int32_t nsite, nsensor, nsensordata, pad0;
+  const int32_t *site_bodyid;     /* [nsite] */
+  const int32_t *site_type;       /* [nsite] geom type numbering: 2 sphere, 3 capsule, 4 ellipsoid, 5 cylinder, 6 box */
+  const double *site_pos;         /* [nsite][3] in the body frame */
+  const double *site_quat;        /* [nsite][4] in the body frame */
+  const double *site_size;        /* [nsite][3] */
+  const int32_t *sensor_type;     /* [nsensor] MGX_SENS_* */
+  const int32_t *sensor_objtype;  /* [nsensor] MGX_OBJ_* */
+  const int32_t *sensor_objid;    /* [nsensor] */
+  const int32_t *sensor_reftype;  /* [nsensor] -1: none */
+  const int32_t *sensor_dim;      /* [nsensor] */
+  const int32_t *sensor_adr;      /* [nsensor] */
+  const double *sensor_cutoff;    /* [nsensor] 0: none */
+  double magnetic[3];
+} mgx_sensor_desc;
+
+int mgx_sensor_configure(mgx_model *m, const mgx_sensor_desc *desc);
+
+/* Outputs of mgx_forward: caller-owned device buffers in the model's real type (ncon, con_geom:
+ * int32); any of them may be NULL. C = mgx_model_info.max_ncon. con_force is mj_contactForce
+ * [ext]: the contact's wrench in the contact frame, decoded from its pyramid rows r0 .. :
+ * f[0] = sum of the rows' forces, f[k] = (force[r0 + 2 (k-1)] - force[r0 + 2 (k-1) + 1]) mu[k-1]
+ * for k = 1 .. condim-1; condim 1: f[0] is the single row's force; a contact that got no rows
+ * (row capacity) has 0. Slots c >= ncon hold 0 (con_geom: -1), so every byte of a selected env's
+ * outputs is defined. */
+typedef struct mgx_forward_out {
+  void *qacc;             /* [N][nv] */
+  void *qfrc_constraint;  /* [N][nv] */
+  int32_t *ncon;          /* [N] */
+  int32_t *con_geom;      /* [N][C][2] */
+  void *con_dist;         /* [N][C] */
+  void *con_pos;          /* [N][C][3] */
+  void *con_frame;        /* [N][C][9] rows: normal, tangent 1, tangent 2 */
+  void *con_force;        /* [N][C][6] */
+} mgx_forward_out;
+
+/* mj_forward at the current state: the forward pass of mgx_step (same stages, LDS layout and
+ * per-env scratch; state->scratch is needed where mgx_step needs it) without the integration.
+ * Runs the model's solver (PGS or Newton) warm-started from state->qacc_warmstart, which it does
+ * not update. MGX_E_UNSUPPORTED for models of more than 64 dofs and for elliptic cones. */
+int mgx_forward(const mgx_model *m, const mgx_state *state, const mgx_forward_out *out, int n_env,
+                const uint8_t *env_mask, void *stream);
+
+/* sensordata [N][nsensordata] in the model's real type. fwd: the outputs of an mgx_forward at the
+ * same state (qacc, ncon, con_geom, con_pos, con_frame and con_force are read); it may be NULL
+ * when the model has no accelerometer, force, torque or touch sensor. A model without sensors
+ * returns MGX_OK and launches nothing. Rows of envs that env_mask deselects are left untouched. */
+int mgx_sensor(const mgx_model *m, const mgx_state *state, const mgx_forward_out *fwd, void *sensordata,
+               int n_env, const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

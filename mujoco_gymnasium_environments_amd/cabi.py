@@ -263,6 +263,40 @@ class PackedRay:
         self.desc = d
 
 
+class MgxSensorDesc(C.Structure):
+    _fields_ = [("nsite", C.c_int32), ("nsensor", C.c_int32), ("nsensordata", C.c_int32), ("pad0", C.c_int32),
+                ("site_bodyid", P_I32), ("site_type", P_I32), ("site_pos", P_F64), ("site_quat", P_F64),
+                ("site_size", P_F64), ("sensor_type", P_I32), ("sensor_objtype", P_I32), ("sensor_objid", P_I32),
+                ("sensor_reftype", P_I32), ("sensor_dim", P_I32), ("sensor_adr", P_I32), ("sensor_cutoff", P_F64),
+                ("magnetic", C.c_double * 3)]
+
+
+class MgxForwardOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ["qacc", "qfrc_constraint", "ncon", "con_geom", "con_dist", "con_pos",
+                                          "con_frame", "con_force"]]
+
+
+class PackedSensor:
+    """Holds an ``MgxSensorDesc`` (mgx_sensor_configure) plus the numpy arrays it points to."""
+
+    def __init__(self, model: Model):
+        A = model.arrays
+        self.arrays = {}
+        d = MgxSensorDesc()
+        d.nsite, d.nsensor, d.nsensordata = len(model.site_names), len(model.sensor_names), int(model.nsensordata)
+        for name, kind in (("site_bodyid", "i"), ("site_type", "i"), ("site_pos", "d"), ("site_quat", "d"),
+                           ("site_size", "d"), ("sensor_type", "i"), ("sensor_objtype", "i"), ("sensor_objid", "i"),
+                           ("sensor_reftype", "i"), ("sensor_dim", "i"), ("sensor_adr", "i"), ("sensor_cutoff", "d")):
+            arr = np.ascontiguousarray(A[name], dtype=_NP[kind]).reshape(-1)
+            if arr.size == 0:
+                arr = np.zeros(1, dtype=_NP[kind])
+            self.arrays[name] = arr
+            setattr(d, name, arr.ctypes.data_as(_PTR[kind]))
+        for i in range(3):
+            d.magnetic[i] = float(model.magnetic[i])
+        self.desc = d
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

@@ -950,6 +950,8 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
   if (m->L.bytes > 160 * 1024) { delete m; return fail(MGX_E_CAPACITY, "per-env LDS exceeds 160 KiB"); }
   int r2 = step_kernels_configure(m);
   if (r2 != MGX_OK) { delete m; return r2; }
+  r2 = forward_kernels_configure(m);
+  if (r2 != MGX_OK) { delete m; return r2; }
   if (m->wide) {
     r2 = wide_kernels_configure(m);
     if (r2 != MGX_OK) { delete m; return r2; }
@@ -979,6 +981,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
 int mgx_model_destroy(mgx_model* m) {
   if (!m) return MGX_OK;
   mgx::ray_release(m);
+  mgx::sensor_release(m);
   if (m->dbuf) (void)hipFree(m->dbuf);
   delete m;
   return MGX_OK;

@@ -38,6 +38,7 @@ struct Hooks {
 };
 Hooks read_hooks();
 struct RayState;  // ray casting tables (mgx_ray.h), owned by the model once mgx_ray_configure ran
+struct SensorState;  // site and sensor tables (mgx_sensor.h), owned by the model once mgx_sensor_configure ran
 }  // namespace mgx
 
 struct mgx_model {
@@ -70,6 +71,7 @@ struct mgx_model {
   bool staged_ok = false;  // the staged soccer pipeline supports this model's capacities
   bool staged_rk_ok = false;  // the staged RK4 pipeline (bipedal) supports this model
   mgx::RayState* ray = nullptr;  // mgx_ray_configure (mgx_ray.hip); freed by ray_release
+  mgx::SensorState* sensor = nullptr;  // mgx_sensor_configure (mgx_sensor.hip); freed by sensor_release
 };
 
 namespace mgx {
@@ -153,6 +155,10 @@ int parkour_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, 
 int pgs_lanes();
 // ray casting (mgx_ray.hip): frees the model's ray tables (mgx_model_destroy)
 void ray_release(mgx_model* m);
+// sensors and mj_forward (mgx_sensor.hip): frees the model's sensor tables (mgx_model_destroy); the
+// dynamic-LDS attributes of the forward kernels (mgx_model_create)
+void sensor_release(mgx_model* m);
+int forward_kernels_configure(const mgx_model* m);
 }  // namespace mgx
 
 #define MGX_WIDE_MSG "nv > 64: this model runs on the wide (two dofs per lane) kernels only"

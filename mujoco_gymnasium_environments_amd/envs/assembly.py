@@ -35,6 +35,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..rays import RayForwarding
+from ..sensors import SensorForwarding
 from ..spaces import Box, EnvBase, policy_action
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets",
@@ -141,7 +142,7 @@ class AssemblyTables:
         return s
 
 
-class AssemblyVectorEnv(RayForwarding):
+class AssemblyVectorEnv(RayForwarding, SensorForwarding):
     """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

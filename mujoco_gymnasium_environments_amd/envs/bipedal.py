@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
+from ..sensors import SensorForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 
@@ -108,7 +109,7 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv(RayForwarding):
+class BipedalVectorEnv(RayForwarding, SensorForwarding):
     """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..rays import RayForwarding
+from ..sensors import SensorForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 
@@ -112,7 +113,7 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv(RayForwarding):
+class DancingVectorEnv(RayForwarding, SensorForwarding):
     """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

@@ -24,6 +24,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
+from ..sensors import SensorForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase, policy_action
 from .sharded import StreamShardedEnv
@@ -113,7 +114,7 @@ class ParkourTables:
         return np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.0, 1.0)])
 
 
-class ParkourVectorEnv(RayForwarding):
+class ParkourVectorEnv(RayForwarding, SensorForwarding):
     """``num_envs`` quadruped_parkour envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 100}

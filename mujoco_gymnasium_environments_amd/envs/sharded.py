@@ -140,6 +140,32 @@ class StreamShardedEnv:
                                  mask=None if mask is None else mask[a:b], stream=cs, out=(depth[a:b], seg[a:b]))
         return depth, (seg if segmentation else None)
 
+    @property
+    def sensors(self):
+        return self.shards[0].sensors
+
+    @property
+    def sensor_slices(self):
+        return self.shards[0].sensor_slices
+
+    def sensordata(self, mask: Optional[torch.Tensor] = None, stream=None):
+        """PhysicsBatch.sensordata over every shard: each shard's rows go into slices of one
+        [N, nsensordata] tensor, allocated once. Like render_depth, everything (the forward kernel
+        included) is launched on the caller's stream."""
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        out = self.__dict__.get("_sensor_out")
+        if out is None:
+            b0 = self.shards[0].batch
+            out = torch.zeros(self.num_envs, int(self.model.nsensordata), dtype=b0.dtype, device=self.device)
+            self._sensor_out = out
+        for (a, b), s in zip(self.bounds, self.shards):
+            s.batch.sensordata(mask=None if mask is None else mask[a:b], stream=cs, out=out[a:b])
+        return out
+
+    def sensor(self, name: str, mask: Optional[torch.Tensor] = None, stream=None):
+        """One sensor's columns of a fresh sensordata(): a view [N, dim]."""
+        return self.sensordata(mask=mask, stream=stream)[:, self.sensor_slices[name]]
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

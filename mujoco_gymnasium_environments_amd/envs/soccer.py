@@ -23,6 +23,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
+from ..sensors import SensorForwarding
 from ..seeding import np_random
 from ..spaces import Box, EnvBase
 from .sharded import StreamShardedEnv
@@ -128,7 +129,7 @@ class SoccerTables:
         return out
 
 
-class SoccerVectorEnv(RayForwarding):
+class SoccerVectorEnv(RayForwarding, SensorForwarding):
     """``num_envs`` humanoid_soccer envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

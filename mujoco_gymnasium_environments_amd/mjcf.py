@@ -44,6 +44,26 @@ INTEGRATORS = {"euler": 0, "rk4": 1, "implicit": 2, "implicitfast": 3}
 CONES = {"pyramidal": 0, "elliptic": 1}
 CAM_FIXED, CAM_TRACK, CAM_TRACKCOM = 0, 1, 2   # mjtCamLight; include/mgx.h MGX_CAM_*
 CAM_MODES = {"fixed": 0, "track": 1, "trackcom": 2, "targetbody": 3, "targetbodycom": 4}
+SITE_TYPES = ("sphere", "capsule", "ellipsoid", "cylinder", "box")   # site_type uses the geom numbering
+# <sensor> elements; a sensor's type code is its index here, the order of the library's list
+# (mgx_sensor_type_name, include/mgx.h MGX_SENS_*): the first 13 are computed on the device
+SENSOR_TYPES = (
+    "jointpos", "jointvel", "framepos", "framequat", "framelinvel", "frameangvel", "gyro", "velocimeter",
+    "magnetometer", "accelerometer", "force", "torque", "touch",
+    "rangefinder", "camprojection", "tendonpos", "tendonvel", "actuatorpos", "actuatorvel", "actuatorfrc",
+    "jointactuatorfrc", "tendonactuatorfrc", "ballquat", "ballangvel", "jointlimitpos", "jointlimitvel",
+    "jointlimitfrc", "tendonlimitpos", "tendonlimitvel", "tendonlimitfrc", "framexaxis", "frameyaxis", "framezaxis",
+    "framelinacc", "frameangacc", "subtreecom", "subtreelinvel", "subtreeangmom", "insidesite", "distance", "normal",
+    "fromto", "contact", "e_potential", "e_kinetic", "clock", "tactile", "plugin", "user")
+SENSOR_NSUPPORTED = 13
+SENSOR_DIMS = {"framepos": 3, "framequat": 4, "framelinvel": 3, "frameangvel": 3, "gyro": 3, "velocimeter": 3,
+               "magnetometer": 3, "accelerometer": 3, "force": 3, "torque": 3, "camprojection": 2, "ballquat": 4,
+               "ballangvel": 3, "framexaxis": 3, "frameyaxis": 3, "framezaxis": 3, "framelinacc": 3,
+               "frameangacc": 3, "subtreecom": 3, "subtreelinvel": 3, "subtreeangmom": 3, "normal": 3, "fromto": 6}
+SENSOR_FRAME = ("framepos", "framequat", "framelinvel", "frameangvel")
+SENSOR_SITE = ("gyro", "velocimeter", "magnetometer", "accelerometer", "force", "torque", "touch")
+# sensor_objtype (include/mgx.h MGX_OBJ_*): body is the inertial frame, xbody the body frame
+SENSOR_OBJTYPES = {"body": 0, "xbody": 1, "joint": 2, "geom": 3, "site": 4}
 MINVAL = 1e-15
 
 
@@ -167,6 +187,7 @@ class Model:
     # options
     timestep: float = 0.002
     gravity: np.ndarray = field(default_factory=lambda: np.array([0, 0, -9.81]))
+    magnetic: np.ndarray = field(default_factory=lambda: np.array([0, -0.5, 0]))
     iterations: int = 100
     tolerance: float = 1e-8
     ls_iterations: int = 50
@@ -190,6 +211,8 @@ class Model:
     actuator_names: List[str] = field(default_factory=list)
     site_names: List[str] = field(default_factory=list)
     cam_names: List[str] = field(default_factory=list)
+    sensor_names: List[str] = field(default_factory=list)
+    nsensordata: int = 0
     geom_material: List[str] = field(default_factory=list)   # material name per geom ("" = none)
     arrays: Dict[str, np.ndarray] = field(default_factory=dict)
 
@@ -333,6 +356,8 @@ class _Compiler:
             m.impratio = float(opt.get("impratio", 1.0))
             if "gravity" in opt.attrib:
                 m.gravity = _floats(opt.get("gravity"), 3)
+            if "magnetic" in opt.attrib:
+                m.magnetic = _floats(opt.get("magnetic"), 3)
 
         bodies: List[dict] = []
         joints: List[dict] = []
@@ -418,8 +443,12 @@ class _Compiler:
                     b["geoms"].append(g["id"])
                 elif ch.tag == "site":
                     sa = self._attrs(ch, childcls, "site")
+                    stype = sa.get("type", "sphere")
+                    if stype not in SITE_TYPES:
+                        raise ValueError(f"site {sa.get('name', '')!r}: unknown type {stype!r}")
                     sites.append(dict(name=sa.get("name", ""), body=bid,
-                                      pos=_floats(sa.get("pos"), 3, [0, 0, 0]), quat=self._orient(sa)))
+                                      pos=_floats(sa.get("pos"), 3, [0, 0, 0]), quat=self._orient(sa),
+                                      type=GEOM_TYPES[stype], size=_floats(sa.get("size"), 3, [0.005] * 3)))
                 elif ch.tag == "camera":
                     ca = self._attrs(ch, childcls, "camera")
                     mode = ca.get("mode", "fixed")
@@ -727,6 +756,8 @@ class _Compiler:
             site_bodyid=np.array([s["body"] for s in sites], np.int32),
             site_pos=np.array([s["pos"] for s in sites]).reshape(-1, 3),
             site_quat=np.array([s["quat"] for s in sites]).reshape(-1, 4),
+            site_size=np.array([s["size"][:3] for s in sites]).reshape(-1, 3),
+            site_type=np.array([s["type"] for s in sites], np.int32),
             geom_group=np.array([g["group"] for g in geoms], np.int32),
             geom_rgba=np.array([g["rgba"] for g in geoms]).reshape(-1, 4),
             cam_bodyid=np.array([c["body"] for c in cams], np.int32),
@@ -743,8 +774,54 @@ class _Compiler:
         m.site_names = [s["name"] for s in sites]
         m.cam_names = [c["name"] for c in cams]
         m.geom_material = [g["material"] for g in geoms]
+        self._sensors(m)
         _set_const(m)
         return m
+
+    def _sensors(self, m: Model) -> None:
+        """<sensor> in document order into the sensor_* tables (mjModel's names). Every element
+        compiles: a type or a reference frame the kernels do not compute is refused later, by
+        mgx_sensor_configure. ``noise`` is not simulated (MuJoCo ignores it too)."""
+        rows = []
+        sec = self.root.find("sensor")
+        for el in (list(sec) if sec is not None else []):
+            sa = self._attrs(el, "main")
+            tag = el.tag
+            code = SENSOR_TYPES.index(tag) if tag in SENSOR_TYPES else SENSOR_TYPES.index("user")
+            dim = int(sa.get("dim", 1)) if tag in ("user", "plugin") else SENSOR_DIMS.get(tag, 1)
+            ref = SENSOR_OBJTYPES.get(sa["reftype"], len(SENSOR_OBJTYPES)) if "reftype" in sa else -1
+            if tag in ("jointpos", "jointvel"):
+                objtype, objid = SENSOR_OBJTYPES["joint"], m.name2id("joint", sa.get("joint", ""))
+                if objid < 0:
+                    raise ValueError(f"sensor {sa.get('name', '')!r}: unknown joint {sa.get('joint')!r}")
+                if m.jnt_type[objid] not in (JNT_HINGE, JNT_SLIDE):
+                    raise ValueError(f"sensor {sa.get('name', '')!r}: {tag} needs a hinge or slide joint")
+            elif tag in SENSOR_FRAME:
+                kind = sa.get("objtype", "")
+                objtype = SENSOR_OBJTYPES.get(kind, len(SENSOR_OBJTYPES))
+                table = {"xbody": "body"}.get(kind, kind)
+                objid = m.name2id(table, sa.get("objname", "")) if table in ("body", "geom", "site") else 0
+                if objid < 0:
+                    raise ValueError(f"sensor {sa.get('name', '')!r}: unknown {kind} {sa.get('objname')!r}")
+            elif tag in SENSOR_SITE:
+                objtype, objid = SENSOR_OBJTYPES["site"], m.name2id("site", sa.get("site", ""))
+                if objid < 0:
+                    raise ValueError(f"sensor {sa.get('name', '')!r}: unknown site {sa.get('site')!r}")
+            else:   # a type the kernels do not compute: the object is not resolved
+                objtype, objid = len(SENSOR_OBJTYPES), 0
+            rows.append(dict(name=sa.get("name", ""), type=code, objtype=objtype, objid=objid, reftype=ref, dim=dim,
+                             cutoff=float(sa.get("cutoff", 0))))
+        dims = np.array([r["dim"] for r in rows], np.int32)
+        m.sensor_names = [r["name"] for r in rows]
+        m.nsensordata = int(dims.sum()) if rows else 0
+        m.arrays.update(dict(
+            sensor_type=np.array([r["type"] for r in rows], np.int32),
+            sensor_objtype=np.array([r["objtype"] for r in rows], np.int32),
+            sensor_objid=np.array([r["objid"] for r in rows], np.int32),
+            sensor_reftype=np.array([r["reftype"] for r in rows], np.int32),
+            sensor_dim=dims,
+            sensor_adr=(np.cumsum(dims) - dims).astype(np.int32),
+            sensor_cutoff=np.array([r["cutoff"] for r in rows], np.float64)))
 
     def _pairs(self, geoms, bodies, weldid, parentid, gtype):
         """Candidate contact pairs in MuJoCo's order: explicit <pair>s, then body pairs

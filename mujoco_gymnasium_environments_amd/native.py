@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(PKG, "libmgx.so")
 CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
            "mgx_dancing.hip",
-           "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip"]
+           "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
@@ -27,7 +27,7 @@ HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mg
            "mgx_bipedal.h", "mgx_dancing.h", "mgx_martial.h", "mgx_internal.h", "mgx_wide.h", "mgx_construction.h",
            "mgx_ray.h"]
 # task headers included by one translation unit only (so editing one rebuilds one object)
-TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"]}
+TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_sensor.h"]}
 
 MGX_OK = 0
 MGX_F32 = 0
@@ -177,6 +177,10 @@ _SIGS = {
     "mgx_ray_scene": ([_VP, C.POINTER(cabi.MgxState), _VP, C.c_uint64, C.c_int, _VP, _VP], C.c_int),
     "mgx_ray_cast": ([_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
     "mgx_ray_camera": ([_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
+    "mgx_sensor_type_name": ([C.c_int], C.c_char_p),
+    "mgx_sensor_configure": ([_VP, C.POINTER(cabi.MgxSensorDesc)], C.c_int),
+    "mgx_forward": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxForwardOut), C.c_int, _VP, _VP], C.c_int),
+    "mgx_sensor": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxForwardOut), _VP, C.c_int, _VP, _VP], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

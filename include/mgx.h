@@ -819,6 +819,58 @@ int mgx_forward(const mgx_model *m, const mgx_state *state, const mgx_forward_ou
 int mgx_sensor(const mgx_model *m, const mgx_state *state, const mgx_forward_out *fwd, void *sensordata,
                int n_env, const uint8_t *env_mask, void *stream);
 
+/* ---- Jacobians, mass matrix, inverse dynamics and energy (MuJoCo's mj_jac*, mj_fullM,
+ * data.qfrc_bias / qfrc_passive / qfrc_actuator, mj_inverse's sum, mj_energyPos / mj_energyVel
+ * [ext]) ----------------------------------------------------------------------------------- */
+/* As above: everything is evaluated at the CURRENT state, as after mj_forward; nothing in
+ * mgx_state is written; no call allocates or synchronises. Buffers are caller-owned device memory,
+ * env-major, in the model's real type. Rows of envs that env_mask deselects are left untouched and
+ * every byte of a selected env's non-NULL outputs is written. Both calls accept every model this
+ * library loads, those of more than 64 dofs included (lanes stride over dofs); a model whose
+ * per-env arrays exceed 160 KiB of LDS is refused with MGX_E_CAPACITY.
+ * Not provided: mj_mulM / mj_solveM (with the dense M these are a batched matrix product / solve),
+ * tendons and equality constraints, mj_jacDot, and MuJoCo's analytic constraint inverse
+ * (mj_invConstraint): the constraint force of mgx_dynamics is an input. */
+#define MGX_JAC_WORLD 0       /* pos is a world point attached to the body: mj_jac */
+#define MGX_JAC_LOCAL 1       /* pos is in the body frame, the point is xpos[b] + xmat[b] pos:
+                                 mj_jacBody (pos = 0), mj_jacSite, mj_jacGeom */
+#define MGX_JAC_BODYCOM 2     /* the point is xipos[b]: mj_jacBodyCom (pos is not read) */
+#define MGX_JAC_SUBTREECOM 3  /* mj_jacSubtreeCom of the subtree rooted at b (pos is not read) */
+
+/* mj_jac for n_point points per env. body, kind: device int32 [n_point], shared by all envs. pos:
+ * [n_point][3] shared by all envs (pos_per_env == 0) or [N][n_point][3] (pos_per_env == 1); NULL
+ * means zeros. Outputs, each nullable: jacp, jacr [N][n_point][3][nv] and point [N][n_point][3],
+ * the world point used. Column d is zero unless dof d moves the point (the body's chain,
+ * body_dofmask; for SUBTREECOM the chains of the subtree's bodies); else jacr[:, d] = cdof_ang[d]
+ * and jacp[:, d] = cdof_lin[d] + cdof_ang[d] x (point - subtree_com[rootid[b]]). SUBTREECOM is
+ * the mass-weighted sum of the body-COM Jacobians over the subtree divided by its mass; its jacr
+ * is written 0. The caller's contract (the tables are device memory, the entry cannot read
+ * them): 0 <= body[p] < nbody and kind[p] is an MGX_JAC_* code; the kernel writes zeros for a
+ * point that breaks it. MGX_E_ARG for n_point < 1, n_env < 0 or a NULL body / kind / state. */
+int mgx_jac(const mgx_model *m, const mgx_state *state, int n_point, const int32_t *body, const int32_t *kind,
+            const void *pos, int pos_per_env, void *jacp, void *jacr, void *point, int n_env,
+            const uint8_t *env_mask, void *stream);
+
+/* Every pointer is nullable; a stage of the kernel runs only when a requested output needs it. */
+typedef struct mgx_dyn_io {
+  const void *qacc;             /* in  [N][nv] (qfrc_inverse) */
+  const void *qfrc_constraint;  /* in  [N][nv] (qfrc_inverse); NULL: 0 */
+  void *M;              /* [N][nv][nv] dense symmetric joint-space inertia, armature included: mj_fullM of qM */
+  void *qfrc_bias;      /* [N][nv] Coriolis, centrifugal and gravity: mj_rne with zero acceleration */
+  void *qfrc_passive;   /* [N][nv] joint damping and springs (hinge, slide, free translation) */
+  void *qfrc_actuator;  /* [N][nv] */
+  void *qfrc_external;  /* [N][nv] qfrc_applied + sum of J' xfrc_applied */
+  void *qfrc_inverse;   /* [N][nv] M qacc + qfrc_bias - qfrc_passive - qfrc_constraint; needs qacc */
+  void *energy;         /* [N][2] potential: -sum m_b g . xipos_b + springs k (q - q_spring)^2 / 2;
+                           kinetic: v' M v / 2 */
+} mgx_dyn_io;
+
+/* With the qacc and qfrc_constraint of an mgx_forward at the same state, qfrc_inverse equals
+ * qfrc_actuator + qfrc_external (MuJoCo's forward / inverse check). MGX_E_ARG when qfrc_inverse
+ * is requested without qacc. */
+int mgx_dynamics(const mgx_model *m, const mgx_state *state, const mgx_dyn_io *io, int n_env,
+                 const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ import torch
 
 from . import cabi, mjcf
 from .native import MGX_F32, MGX_F64, check, lib
+from .dynamics import DynamicsMethods
 from .rays import RayMethods
 from .sensors import SensorMethods
 
@@ -58,7 +59,7 @@ class NativeModel:
             self.handle = None
 
 
-class PhysicsBatch(RayMethods, SensorMethods):
+class PhysicsBatch(RayMethods, SensorMethods, DynamicsMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

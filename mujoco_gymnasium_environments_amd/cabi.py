@@ -297,6 +297,14 @@ class PackedSensor:
         self.desc = d
 
 
+MGX_JAC_WORLD, MGX_JAC_LOCAL, MGX_JAC_BODYCOM, MGX_JAC_SUBTREECOM = 0, 1, 2, 3  # include/mgx.h point kinds
+
+
+class MgxDynIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ["qacc", "qfrc_constraint", "M", "qfrc_bias", "qfrc_passive",
+                                          "qfrc_actuator", "qfrc_external", "qfrc_inverse", "energy"]]
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

@@ -159,6 +159,8 @@ void ray_release(mgx_model* m);
 // dynamic-LDS attributes of the forward kernels (mgx_model_create)
 void sensor_release(mgx_model* m);
 int forward_kernels_configure(const mgx_model* m);
+// Jacobians and dynamics (mgx_dyn.hip): the dynamic-LDS attributes of its kernels (mgx_model_create)
+int dyn_kernels_configure(const mgx_model* m);
 }  // namespace mgx
 
 #define MGX_WIDE_MSG "nv > 64: this model runs on the wide (two dofs per lane) kernels only"

@@ -34,6 +34,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
+from ..dynamics import DynamicsForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..spaces import Box, EnvBase, policy_action
@@ -142,7 +143,7 @@ class AssemblyTables:
         return s
 
 
-class AssemblyVectorEnv(RayForwarding, SensorForwarding):
+class AssemblyVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
     """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

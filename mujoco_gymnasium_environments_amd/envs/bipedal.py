@@ -30,6 +30,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
+from ..dynamics import DynamicsForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..seeding import np_random
@@ -109,7 +110,7 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv(RayForwarding, SensorForwarding):
+class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
     """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

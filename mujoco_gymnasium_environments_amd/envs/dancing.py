@@ -30,6 +30,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
+from ..dynamics import DynamicsForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..seeding import np_random
@@ -113,7 +114,7 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv(RayForwarding, SensorForwarding):
+class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
     """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

@@ -166,6 +166,62 @@ class StreamShardedEnv:
         """One sensor's columns of a fresh sensordata(): a view [N, dim]."""
         return self.sensordata(mask=mask, stream=stream)[:, self.sensor_slices[name]]
 
+    def jac_points(self, **kw):
+        """PhysicsBatch.jac_points (the shards share one model and device, so one points object
+        serves them all)."""
+        return self.shards[0].batch.jac_points(**kw)
+
+    def _jac_over_shards(self, call, key, n_point, mask, stream):
+        from ..dynamics import JacResult
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        cache = self.__dict__.setdefault("_jac_out", {})
+        if key not in cache:
+            b0 = self.shards[0].batch
+            cache[key] = JacResult(self.num_envs, n_point, int(self.model.nv), b0.dtype, self.device)
+        full = cache[key]
+        for (a, b), s in zip(self.bounds, self.shards):
+            call(s.batch, a, b, None if mask is None else mask[a:b], cs, full.rows(a, b))
+        return full
+
+    def jac(self, points, mask: Optional[torch.Tensor] = None, stream=None):
+        """PhysicsBatch.jac over every shard: each shard's rows go into slices of one JacResult,
+        allocated once per points object. Like sensordata, everything is launched on the caller's
+        stream."""
+        self.__dict__.setdefault("_jac_points", {})[id(points)] = points  # keeps the cache key's id alive
+        return self._jac_over_shards(lambda bt, a, b, m, cs, out: bt.jac(points, mask=m, stream=cs, out=out),
+                                     ("points", id(points)), len(points), mask, stream)
+
+    def jac_world(self, body_ids, pos: torch.Tensor, mask: Optional[torch.Tensor] = None, stream=None):
+        """PhysicsBatch.jac_world over every shard (``pos`` [N, P, 3])."""
+        p = int(pos.shape[1])
+        return self._jac_over_shards(
+            lambda bt, a, b, m, cs, out: bt.jac_world(body_ids, pos[a:b], mask=m, stream=cs, out=out),
+            ("world", p), p, mask, stream)
+
+    def dynamics(self, qacc: Optional[torch.Tensor] = None, qfrc_constraint: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None, stream=None, only=None):
+        """PhysicsBatch.dynamics over every shard: each shard's rows go into slices of one set of
+        tensors, allocated once; launched on the caller's stream."""
+        from ..dynamics import DYN_OUTPUTS, DynamicsResult, alloc_dynamics
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        full = self.__dict__.get("_dyn_out")
+        if full is None:
+            b0 = self.shards[0].batch
+            full = self._dyn_out = alloc_dynamics(self.num_envs, int(self.model.nv), b0.dtype, self.device)
+        part = None
+        for (a, b), s in zip(self.bounds, self.shards):
+            part = s.batch.dynamics(qacc=None if qacc is None else qacc[a:b],
+                                    qfrc_constraint=None if qfrc_constraint is None else qfrc_constraint[a:b],
+                                    mask=None if mask is None else mask[a:b], stream=cs, only=only,
+                                    out=full.rows(a, b))
+        return DynamicsResult(**{f: getattr(full, f) for f in DYN_OUTPUTS if getattr(part, f) is not None})
+
+    def mass_matrix(self, mask: Optional[torch.Tensor] = None, stream=None):
+        return self.dynamics(mask=mask, stream=stream, only=("M",)).M
+
+    def energy(self, mask: Optional[torch.Tensor] = None, stream=None):
+        return self.dynamics(mask=mask, stream=stream, only=("energy",)).energy
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

@@ -22,6 +22,7 @@ import torch
 from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
+from ..dynamics import DynamicsForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..seeding import np_random
@@ -129,7 +130,7 @@ class SoccerTables:
         return out
 
 
-class SoccerVectorEnv(RayForwarding, SensorForwarding):
+class SoccerVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
     """``num_envs`` humanoid_soccer envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

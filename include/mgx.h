@@ -871,6 +871,63 @@ typedef struct mgx_dyn_io {
 int mgx_dynamics(const mgx_model *m, const mgx_state *state, const mgx_dyn_io *io, int n_env,
                  const uint8_t *env_mask, void *stream);
 
+/* ---- finite-difference transition derivatives (MuJoCo's mjd_transitionFD / mjd_stepFD [ext]) --- */
+/* The discrete-time linearisation x' ~ A dx + B du of nsub mj_steps from the current state. The
+ * state tangent is x = (dq [nv], qvel [nv]) (the models have no actuator activations), so
+ * A = dx'/dx is [N][2nv][2nv] and B = dx'/dctrl is [N][2nv][nu], row-major as MuJoCo lays them
+ * out, in the model's real type T. x' is the state after nsub >= 1 mgx_step substeps (10 for the
+ * physics of one parkour or assembly env step).
+ *   column k < nv         qpos <- mj_integratePos(qpos, eps e_k): hinge, slide and free translation
+ *                         add eps to one entry (one add in T); free and ball rotations compose
+ *                         quat <- normalize(quat o (cos(eps/2), sin(eps/2) e_axis)), local frame
+ *   column nv <= k < 2nv  qvel[k - nv] + eps
+ *   column 2nv + u        ctrl[u] + eps
+ *   row block 0           mj_differentiatePos(q'_perturbed, q'_nominal) / step: scalar coordinates
+ *                         subtract; a quaternion gives the rotation vector of conj(q'_nom) o q'_pert,
+ *                         angle 2 atan2(|v|, w) wrapped to (-pi, pi], 0 for a zero vector
+ *   row block 1           (qvel'_perturbed - qvel'_nominal) / step
+ * Every entry is (a - b) / step, a true division in T by the signed step taken (+-eps). With
+ * MGX_FD_CENTERED a column is the difference of its +eps and -eps steps divided by 2 eps.
+ * Control limits: the nominal ctrl is the value the step uses, clamped to actuator_ctrlrange where
+ * ctrllimited, and a perturbation that would leave that range is not taken: forward mode uses +eps
+ * if it stays inside, else -eps, else the column is 0; centred mode uses both sides if both stay
+ * inside, else the one that does (a one-sided difference), else the column is 0.
+ * Every perturbed step starts from the nominal qacc_warmstart, time, qfrc_applied and xfrc_applied.
+ * Nothing in the caller's mgx_state is written (qacc_warmstart, time, warning and overflow
+ * included). A nominal or perturbed step that hits the bad-state auto-reset makes its column
+ * meaningless: `warning` counts those steps per env, 0 = every column is valid.
+ * As above: rows of envs that env_mask deselects are left untouched, every byte of a selected env's
+ * non-NULL outputs is written, and the call is asynchronous on the stream and neither allocates
+ * nor synchronises.
+ * Not provided: sensor derivatives (MuJoCo's C and D), analytic derivatives (mjd_smooth_vel) and
+ * derivatives of a task's reward or observation. */
+#define MGX_FD_CENTERED 1
+
+typedef struct mgx_fd_io {
+  double eps;                    /* > 0; used in the model's real type */
+  int32_t flags, nsub;           /* MGX_FD_* bits; mj_steps per transition, >= 1 */
+  void *A, *B;                   /* [N][2nv][2nv], [N][2nv][nu]; each nullable */
+  void *next_qpos, *next_qvel;   /* [N][nq], [N][nv]: the nominal next state; nullable */
+  int32_t *warning;              /* [N], nullable */
+  void *workspace;               /* device memory, mgx_transition_fd_bytes(m, slots) bytes */
+  uint64_t workspace_bytes;
+  int32_t slots, pad0;
+} mgx_fd_io;
+
+/* The workspace holds `slots` virtual envs, each a complete mgx_state (qpos, qvel, qacc_warmstart,
+ * ctrl, qfrc_applied, xfrc_applied, time, warning, overflow) plus scratch_bytes_per_env of solver
+ * scratch where the model needs it; its contents need no initialisation. One env takes
+ * C = 1 + K virtual envs (centred: 1 + 2 K), K = 2 nv + nu; the call processes floor(slots / C)
+ * envs per pass and loops on the host, every launch on the one stream, so the caller bounds the
+ * memory with `slots` and the call stays graph-capturable. */
+int64_t mgx_transition_fd_bytes(const mgx_model *m, int slots);
+
+/* MGX_E_ARG for slots < C, eps <= 0, nsub < 1, unknown flag bits, a NULL state or io, or a
+ * workspace smaller than mgx_transition_fd_bytes(m, slots). With no output requested the call
+ * returns MGX_OK and launches nothing. */
+int mgx_transition_fd(const mgx_model *m, const mgx_state *state, const mgx_fd_io *io, int n_env,
+                      const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,15 @@ class MgxDynIO(C.Structure):
                                           "qfrc_actuator", "qfrc_external", "qfrc_inverse", "energy"]]
 
 
+MGX_FD_CENTERED = 1  # include/mgx.h mgx_fd_io.flags
+
+
+class MgxFdIO(C.Structure):
+    _fields_ = [("eps", C.c_double), ("flags", C.c_int32), ("nsub", C.c_int32), ("A", C.c_void_p), ("B", C.c_void_p),
+                ("next_qpos", C.c_void_p), ("next_qvel", C.c_void_p), ("warning", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("slots", C.c_int32), ("pad0", C.c_int32)]
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

@@ -35,6 +35,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..dynamics import DynamicsForwarding
+from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..spaces import Box, EnvBase, policy_action
@@ -143,7 +144,7 @@ class AssemblyTables:
         return s
 
 
-class AssemblyVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
+class AssemblyVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
     """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..dynamics import DynamicsForwarding
+from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..seeding import np_random
@@ -110,7 +111,7 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
+class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
     """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..dynamics import DynamicsForwarding
+from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
 from ..seeding import np_random
@@ -114,7 +115,7 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding):
+class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
     """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

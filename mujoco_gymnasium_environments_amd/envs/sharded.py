@@ -222,6 +222,20 @@ class StreamShardedEnv:
     def energy(self, mask: Optional[torch.Tensor] = None, stream=None):
         return self.dynamics(mask=mask, stream=stream, only=("energy",)).energy
 
+    def transition_fd(self, mask: Optional[torch.Tensor] = None, stream=None, only=None, **kw):
+        """PhysicsBatch.transition_fd over every shard, into slices of one set of tensors."""
+        from ..transitions import FD_OUTPUTS, TransitionResult, alloc_transition
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        full = self.__dict__.get("_fd_out")
+        if full is None:
+            b0, m = self.shards[0].batch, self.model
+            full = self._fd_out = alloc_transition(self.num_envs, int(m.nq), int(m.nv), int(m.nu), b0.dtype, self.device)
+        part = None
+        for (a, b), s in zip(self.bounds, self.shards):
+            part = s.batch.transition_fd(mask=None if mask is None else mask[a:b], stream=cs, only=only,
+                                         out=full.rows(a, b), **kw)
+        return TransitionResult(**{f: getattr(full, f) for f in FD_OUTPUTS if getattr(part, f) is not None})
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

@@ -590,7 +590,8 @@ static int wide_arena_bytes(const mgx_model* m) {
 
 // Staged-step workspace layout for (model, n_env, banks); offsets in bytes, 256-aligned. rk: the
 // RK4 staged step's extra arrays (stage carry, template scratch); nobs: floats per bank observation.
-size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P, bool rk, int nobs) {
+size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P, bool rk, int nobs,
+                             int split_default) {
   int rb = m->precision == MGX_F32 ? 4 : 8;
   int nq = m->precision == MGX_F32 ? m->mf.nq : m->md.nq;
   int nv = m->precision == MGX_F32 ? m->mf.nv : m->md.nv;
@@ -662,8 +663,28 @@ size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks,
                 (H.pgs_wpc == 4 ? staged_pgs_lds_bytes(m, p.capE, pgs_lanes(), 0, mgx_twl(false))
                                 : 160 * 1024 / H.pgs_wpc);
   if (p.hmain) p.warena = 0;
+  // row-split waves (pgs_group SPLIT): the main launch's slots of at least split_blocks blocks get a
+  // wave each. The threshold never exceeds capE / 4 + 1, so every slot over capE rows is split and
+  // neither the heavy-slot path (hmain) nor the wide launch is needed. A split wave's LDS is one
+  // slot of up to maxE rows (scalars, forces, table), which must fit the main launch's allocation
+  // of four slots x capE rows so that the launch keeps its waves per CU; only the MGX_PGS_LDS_ROWS
+  // test hook, whose few rows make that allocation tiny, raises the launch's LDS to it instead.
+  p.split_blocks = 0;
+  const int split = H.pgs_split_blocks >= 0 ? H.pgs_split_blocks : split_default;
+  if (!rk && !p.sqg && !H.pgs_lds_b && pgs_lanes() == 16 && split > 0) {
+    const int one = staged_pgs_lds_bytes(m, p.maxE, 64, 0, mgx_twl(false));
+    int main_lds = staged_pgs_lds_bytes(m, p.capE, 16, 0, mgx_twl(false));
+    if (p.hmain) main_lds = std::max(main_lds, staged_pgs_lds_bytes(m, p.maxE, 16, 1, mgx_twl(false)));
+    // a split wave addresses its slot's B with 32-bit byte offsets from the slot's base (pgs_b_at)
+    const bool b32 = (uint64_t)p.bcap * (uint64_t)rb < (1ull << 32);
+    if (b32 && one <= (cap_env ? 160 * 1024 : main_lds)) {
+      p.split_blocks = std::min(split, p.capE / 4 + 1);
+      p.hmain = 0;
+      p.warena = 0;
+    }
+  }
   p.prio_rows = H.pgs_prio_rows > 0 ? H.pgs_prio_rows : p.capE;
-  p.nbk = (p.hmain ? p.maxE : p.capE) / 4 + 1;
+  p.nbk = (p.hmain || p.split_blocks ? p.maxE : p.capE) / 4 + 1;
   p.o_hist = take((size_t)(p.maxE / 4 + 1) * 4);
   p.o_blist = take((size_t)(p.maxE / 4 + 1) * S * 4);
   p.o_scal = take(S * p.maxE * MGX_SCAL * rb);
@@ -694,7 +715,7 @@ size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks,
   return off;
 }
 static size_t make_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P) {
-  return make_staged_pipe(m, ws, n_env, banks, P, false, 80);
+  return make_staged_pipe(m, ws, n_env, banks, P, false, 80, MGX_PGS_SPLIT_BLOCKS);
 }
 
 // LDS of one solver wave holding `rows` rows per slot (main launch: min(max_nefc,
@@ -727,6 +748,7 @@ mgx::Hooks mgx::read_hooks() {
   h.pgs_wide_lds = get("MGX_PGS_WIDE_LDS", 1);
   h.pgs_spw = get("MGX_PGS_SPW", 0);
   h.pgs_prio_rows = get("MGX_PGS_PRIO_ROWS", 0);
+  h.pgs_split_blocks = get("MGX_PGS_SPLIT_BLOCKS", -1);
   h.tight_bp = get("MGX_TIGHT_BROADPHASE", -1);
   h.pgs_wpc = get("MGX_PGS_WPC", 4);
   if (h.pgs_wpc < 4 || h.pgs_wpc > 16) h.pgs_wpc = 4;
@@ -799,9 +821,11 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   const int wgrid = 64 / pgs_lanes() * MGX_PGS_WIDE_GRID, wlds = pgs_lds_bytes(m, P.maxE);
   int mlds = H.pgs_lds_b ? P.arena : pgs_lds_bytes(m, P.capE, P.sqg);
   if (P.hmain) mlds = std::max(mlds, pgs_lds_bytes(m, P.maxE, 1));  // the heavy slots' SQG layout
+  // a split wave's one slot of up to maxE rows (larger only under the MGX_PGS_LDS_ROWS test hook)
+  if (P.split_blocks) mlds = std::max(mlds, staged_pgs_lds_bytes(m, P.maxE, 64, 0, mgx_twl(false)));
   // occupancy probe: MGX_PGS_LDS_PAD pads the main solver launch's LDS (fewer waves per CU)
   if (H.pgs_lds_pad > mlds && H.pgs_lds_pad <= 96 * 1024) mlds = H.pgs_lds_pad;
-  if (!H.pgs_lds_b && (P.maxE <= P.capE || P.hmain)) {
+  if (!H.pgs_lds_b && (P.maxE <= P.capE || P.hmain || P.split_blocks)) {
     // every slot fits the main launch (the default capacity): no wide launch at all
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H);
   } else if (SideStream* side = (!H.pgs_lds_b && H.side_stream) ? side_stream(st) : nullptr) {

@@ -31,7 +31,9 @@ struct Hooks {
   int pgs_spw = 0;       // MGX_PGS_SPW: slots per solver wave (debug)
   int pgs_wpc = 4;       // MGX_PGS_WPC: main solver launch's waves per CU its LDS rows are sized for
   int pgs_prio_rows = 0; // MGX_PGS_PRIO_ROWS: rows above which a main-launch solver wave raises its priority
-  int tight_bp = -1;     // MGX_TIGHT_BROADPHASE: box prefilters in the broadphase (-1: by the pair count)
+  int pgs_split_blocks = -1;  // MGX_PGS_SPLIT_BLOCKS: blocks from which a main-launch slot is solved row-split,
+                              // one slot per wave (-1: the pipeline's default; 0: off; 1: every slot)
+  int tight_bp = -1;    // MGX_TIGHT_BROADPHASE: box prefilters in the broadphase (-1: by the pair count)
   int side_stream = 1;   // MGX_SIDE_STREAM: the wide solver launch on a side stream
   int gcon = 1;          // MGX_GCON: the row builder's contact points in the pipe (0: in LDS)
   int rows_lds = 0;      // MGX_ROWS_LDS: pad the row builder's LDS (occupancy probe)
@@ -129,7 +131,10 @@ void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const So
 int staged_kernels_configure(int precision, int ls, int lf, int settle);
 // staged-step workspace layout (mgx_api.hip) and the LDS of one solver wave holding `rows` rows
 // per slot with `lps` lanes per slot and `tw` table words per block
-size_t make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P, bool rk, int nobs);
+// split_default: the pipeline's row-split threshold in blocks when MGX_PGS_SPLIT_BLOCKS is not set
+// (Pipe.split_blocks; 0: off)
+size_t make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P, bool rk, int nobs,
+                        int split_default = 0);
 // sqg: row scalars in the pipe, only the forces in LDS (the RK4 pipeline; soccer at full capacity)
 // twl: block-table words per block in LDS (mgx_twl: 8 for the 8-dof group layout, 4 dof-granular)
 int staged_pgs_lds_bytes(const mgx_model* m, int rows, int lps, int sqg, int twl);

@@ -27,6 +27,9 @@ namespace mgx {
 
 constexpr int PK_LPS = 16;  // solver lanes per slot
 constexpr int PK_OBS = 95;  // parkour_env.py:396-468
+// slots of at least this many 4-row blocks are solved row-split, one per wave (Pipe.split_blocks;
+// 40 / 56 / 72 measured alike against chains of up to 85 blocks)
+constexpr int PK_SPLIT_BLOCKS = 56;
 enum { PK_SETTLE_RESET = 0, PK_SETTLE_FIXUP = 1 };
 enum { PK_SUBSTEPS = 10 };  // frame_skip (parkour_env.py:367-368)
 
@@ -387,15 +390,17 @@ int step_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms,
                 uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
   const int banks = autoreset ? e->banks : 0;
-  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, false, PK_OBS);
+  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, false, PK_OBS, PK_SPLIT_BLOCKS);
   if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_parkour_workspace_bytes");
   // parkour_staged_ok: every slot is solved by the main launch (a slot over capE rows, e.g. the
-  // qpos0 pile-up after a bad-state reset, in its heaviest-first list with its scalars read from
-  // the pipe: Pipe.hmain)
+  // qpos0 pile-up after a bad-state reset, in its heaviest-first list: row-split, one slot per wave,
+  // Pipe.split_blocks; with MGX_PGS_SPLIT_BLOCKS=0 its scalars read from the pipe, Pipe.hmain)
   const int slots = n_env * (1 + banks);
   const T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
-  const int mlds = std::max(staged_pgs_lds_bytes(m, P.capE, PK_LPS, 0, 8),
-                           P.hmain ? staged_pgs_lds_bytes(m, P.maxE, PK_LPS, 1, 8) : 0);
+  // Pipe.split_blocks: a row-split wave's one slot of maxE rows
+  const int mlds = std::max({staged_pgs_lds_bytes(m, P.capE, PK_LPS, 0, 8),
+                            P.hmain ? staged_pgs_lds_bytes(m, P.maxE, PK_LPS, 1, 8) : 0,
+                            P.split_blocks ? staged_pgs_lds_bytes(m, P.maxE, 64, 0, 8) : 0});
   const int spw = 64 / PK_LPS, grid = (slots + spw - 1) / spw;
   for (int k = 0; k < PK_SUBSTEPS; k++) {
     hipLaunchKernelGGL(k_pk_rows<T>, dim3(slots), dim3(64), m->Ls.bytes, st, Ms, ids, *s, action, e->action_f64, n_env,
@@ -421,7 +426,7 @@ int reset_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms
                  const ParkourIds<T>& ids, const mgx_state* s, const mgx_parkour_env* e, const T* draws, float* obs,
                  uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
-  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, false, PK_OBS);
+  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, false, PK_OBS, PK_SPLIT_BLOCKS);
   if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_parkour_workspace_bytes");
   const T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
   MGX_PK_EPL(pk_epl(M), hipLaunchKernelGGL((k_pk_settle<T, E>), dim3(n_env), dim3(64), pk_settle_lds(m, P), st, Ms, Mf,
@@ -434,7 +439,7 @@ int reset_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms
 template <typename T>
 int configure_t(const mgx_model* m) {
   Pipe P;
-  make_staged_pipe(m, nullptr, 1, 1, &P, false, PK_OBS);
+  make_staged_pipe(m, nullptr, 1, 1, &P, false, PK_OBS, PK_SPLIT_BLOCKS);
   const int pl = staged_pgs_lds_bytes(m, P.maxE, PK_LPS, 0, 8);
   if (pl > 160 * 1024) return fail(MGX_E_CAPACITY, "staged parkour solver LDS exceeds 160 KiB");
   int rc = mgx_set_lds(k_pk_rows<T>, m->Ls.bytes) | mgx_set_lds(k_pk_finish<T>, m->Lf.bytes) |
@@ -457,8 +462,8 @@ bool parkour_staged_ok(const mgx_model* m) {
   const int nv = m->precision == MGX_F32 ? m->mf.nv : m->md.nv;
   if (!m->staged_ok || nv > 64 || pgs_lanes() != PK_LPS || m->hooks.pgs_lds_b) return false;
   Pipe P;
-  make_staged_pipe(m, nullptr, 1, 1, &P, false, PK_OBS);
-  return !P.sqg && (P.maxE <= P.capE || P.hmain);
+  make_staged_pipe(m, nullptr, 1, 1, &P, false, PK_OBS, PK_SPLIT_BLOCKS);
+  return !P.sqg && (P.maxE <= P.capE || P.hmain || P.split_blocks);
 }
 
 int parkour_staged_configure(const mgx_model* m) {
@@ -492,14 +497,14 @@ int parkour_reset_staged(const mgx_model* m, const mgx_state* s, const mgx_parko
 int64_t parkour_workspace_bytes(const mgx_model* m, int n_env, int banks) {
   if (!m || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
   if (!parkour_staged_ok(m)) return fail(MGX_E_UNSUPPORTED, "staged parkour step: model outside the staged pipeline");
-  return (int64_t)make_staged_pipe(m, nullptr, n_env, banks, nullptr, false, PK_OBS);
+  return (int64_t)make_staged_pipe(m, nullptr, n_env, banks, nullptr, false, PK_OBS, PK_SPLIT_BLOCKS);
 }
 
 int parkour_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks, hipStream_t st) {
   if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
   if (!parkour_staged_ok(m)) return fail(MGX_E_UNSUPPORTED, "staged parkour step: model outside the staged pipeline");
   Pipe P;
-  const size_t need = make_staged_pipe(m, workspace, n_env, banks, &P, false, PK_OBS);
+  const size_t need = make_staged_pipe(m, workspace, n_env, banks, &P, false, PK_OBS, PK_SPLIT_BLOCKS);
   if (bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_parkour_workspace_bytes");
   MGX_HIPCHK(hipMemsetAsync(workspace, 0, need, st));
   const size_t nb = (size_t)n_env * (banks > 0 ? banks : 1);

@@ -9,7 +9,8 @@
 //                                       B rows + row scalars -> HBM, carry -> HBM (27 KB LDS)
 //   S2  k_pgs_groups    16 lanes / slot PGS sweeps, 4 slots / wave, with the slots' B copied
 //                                       once into an LDS arena (global-B launch for waves whose
-//                                       slots do not fit), v = B'f in registers
+//                                       slots do not fit), v = B'f in registers; the heaviest
+//                                       slots one per wave, one row of a block per lane group
 //   S3  k_soccer_finish wave per env    qacc, checkAcc, Euler, post-logic, autoreset (7 KB LDS)
 //   S4  k_soccer_fixup  wave per listed env, monolithic: reset whose bank was not ready
 //
@@ -45,6 +46,7 @@ __host__ __device__ constexpr int mgx_twl(bool dofb) { return dofb ? 4 : 8; }  /
 #define MGX_PGS_RING 2         // global-B solver: register ring of 4-row blocks (RING - 1 in flight; 3 and 4 measured no faster)
 #define MGX_PGS_RING_LDS 2     // LDS-B solver: one block in flight covers the LDS latency
 #define MGX_PGS_LDS_ROWS 192   // rows per slot the main solver launch keeps in LDS (2 waves / CU in fp64)
+#define MGX_PGS_SPLIT_BLOCKS 40  // soccer main launch: slots of at least this many blocks are solved row-split, one per wave
 #define MGX_PGS_WIDE_GRID 256  // waves of the global-B launch (slots over MGX_PGS_LDS_ROWS, waves over their arena)
 #define MGX_PGS_WIDE_LDS_GRID 32  // waves of the wide launch with LDS-resident B (one slot per wave)
 #define MGX_PGS_ARENA_F64 49152  // LDS arena per main-launch solver wave of 4 slots, fp64 (tools/pgs_census.py)
@@ -68,6 +70,11 @@ struct Pipe {
   int hmain;           // 1: slots over capE rows stay in the main launch's heaviest-first list; a wave
                        // holding one runs with its row scalars read from the pipe (SQG), whose LDS
                        // (forces + table for maxE rows) fits the wave's capE-row allocation
+  int split_blocks;    // > 0: the main launch solves each listed slot of at least this many 4-row blocks
+                       // alone in its wave, one row of every block per lane group (pgs_group SPLIT).
+                       // At most capE / 4 + 1, so a slot over capE rows is always split (no hmain, no
+                       // wide launch); the split wave's one slot of up to maxE rows has its scalars,
+                       // forces and table in the wave's LDS (MGX_PGS_SPLIT_BLOCKS; 0: off)
   int warena;          // > 0: LDS bytes of the wide launch's one-slot waves, which solve a slot of
                        // more than capE rows with its B, scalars and table copied into LDS (the
                        // latency-bound chain of a heavy slot reads LDS instead of L2 / MALL)
@@ -93,7 +100,9 @@ struct Pipe {
   size_t o_rk, o_rks, o_rkw, o_tscr;
   template <typename X> __device__ __forceinline__ X* at(size_t off) const { return reinterpret_cast<X*>(base + off); }
   // [0] fixup count, [1] solver-list count, [2] wide-solver-list count, [3] / [4] the last
-  // step's list sizes, [5] RK4 step: fixup count (k_pgs_groups clears [0] at every launch)
+  // step's list sizes, [5] RK4 step: fixup count (k_pgs_groups clears [0] at every launch),
+  // [6] / [7] since the workspace was initialised: slots over capE rows solved in split mode /
+  // listed by the row builder (equal when split_blocks > 0; tests/test_gpu_pgs_split.py)
   __device__ __forceinline__ int* ctr() const { return at<int>(o_ctr); }
 };
 
@@ -535,8 +544,9 @@ __device__ __forceinline__ void stage_rows(const DevModel<T>& m, Env<T>& e, cons
       g_mgx_prof[slot * 32 + 25] += e.overflow != 0;
     }
 #endif
+    if (list_slot && ne > P.capE) atomicAdd(P.ctr() + 7, 1);
     if (!list_slot) {
-    } else if (ne > P.capE && !P.hmain) {  // rare: more rows than the main solver launch keeps in LDS
+    } else if (ne > P.capE && !P.hmain && !P.split_blocks) {  // rare: more rows than the main solver launch keeps in LDS
       int idx = atomicAdd(P.ctr() + 2, 1);
       P.at<int>(P.o_k2big)[idx] = slot;
     } else if (ne > 0) {
@@ -653,18 +663,26 @@ typedef float mgx_f2 __attribute__((ext_vector_type(2)));
 // loaded here is the latest one.
 // sq: the row scalars ([b][f][R][1/AR][AR/2] x 4 per block; LDS arena or the pipe in global
 // memory), fb: the forces, FS reals per block (the LDS copy the sweeps update)
-template <typename T, int EPL, int LPS, int FS>
+// U32 (row-split waves): B is one wave-uniform slot's, so an entry's address is that base (an SGPR
+// pair) plus the lane's 32-bit byte offset, without 64-bit per-lane address arithmetic; a slot's B
+// extent (Pipe.bcap reals) fits 32 bits (make_staged_pipe)
+template <bool U32, typename T>
+__device__ __forceinline__ const T* pgs_b_at(const T* Bsl, uint32_t entry) {
+  if constexpr (U32) return reinterpret_cast<const T*>(reinterpret_cast<const char*>(Bsl) + entry * (uint32_t)sizeof(T));
+  else return Bsl + entry;
+}
+template <typename T, int EPL, int LPS, int FS, bool U32 = false>
 __device__ __forceinline__ void pgs_load_block(PgsBlk<T, EPL>& k, const T* Bsl, const T* sq, const T* fb,
                                                const PgsTab<EPL>& t, int blk, int sblk, int j) {
   // the table entry of a block past the slot's end points at the zero group (A included);
   // every load is one 16-byte vector load at a table offset (Bsl: the slot's B in the LDS
   // arena, or in global memory for the global-B launch)
   typedef typename Vec4T<T>::type V4;
-  const V4* pa = reinterpret_cast<const V4*>(Bsl + t.a);
+  const V4* pa = reinterpret_cast<const V4*>(pgs_b_at<U32>(Bsl, t.a));
   k.a0 = pa[0];
   k.a1 = pa[1];
 #pragma unroll
-  for (int d = 0; d < EPL; d++) k.b[d] = *reinterpret_cast<const V4*>(Bsl + t.g[d]);
+  for (int d = 0; d < EPL; d++) k.b[d] = *reinterpret_cast<const V4*>(pgs_b_at<U32>(Bsl, t.g[d]));
   const V4* q = reinterpret_cast<const V4*>(sq + 4 * MGX_SCAL * sblk);
   k.qb = q[0];
   k.qf = *reinterpret_cast<const V4*>(fb + FS * blk);
@@ -714,17 +732,81 @@ __device__ __forceinline__ void pgs_update(const PgsBlk<T, EPL>& k, T (&v)[EPL],
   }
 }
 
-template <typename T, int EPL, int LPS>
-__device__ __forceinline__ void pgs_block(const PgsBlk<T, EPL>& k, T (&v)[EPL], T* fblk, bool ok0, T& impr) {
+// Row-split mode (one slot per wave, LPS = 16): lane group g = lane / 16 owns row g of every block
+// for the dot and its reduction. PgsRow holds the group's own row of B at the lane's dofs: one
+// real per register entry, loaded at the vector load's table offset plus g reals (same cache line)
+// rather than picked out of the four-row vector with selects.
+template <typename T, int EPL>
+struct PgsRow {
+  T b[EPL];
+};
+// g: the lane group's row of the block; issued just before the block's pgs_load_block, whose
+// scheduling barrier keeps both where they are (uniform base + 32-bit offset, as its U32 loads)
+template <typename T, int EPL>
+__device__ __forceinline__ void pgs_load_row(PgsRow<T, EPL>& r, const T* Bsl, uint32_t g, const PgsTab<EPL>& t) {
+#pragma unroll
+  for (int d = 0; d < EPL; d++) r.b[d] = *pgs_b_at<true>(Bsl, t.g[d] + g);
+}
+// the group's row dot: the FMA chain of pgs_dots for that row (same order, same start at zero)
+template <int EPL>
+__device__ __forceinline__ double pgs_row_dot(const PgsRow<double, EPL>& r, const double (&v)[EPL]) {
+  double x = 0;
+#pragma unroll
+  for (int d = 0; d < EPL; d++) x += r.b[d] * v[d];
+  return x;
+}
+template <int EPL>
+__device__ __forceinline__ float pgs_row_dot(const PgsRow<float, EPL>& r, const float (&v)[EPL]) {
+  float x = 0.f;  // one lane of pgs_dots' packed FMA
+#pragma unroll
+  for (int d = 0; d < EPL; d++) x = __builtin_fmaf(r.b[d], v[d], x);
+  return x;
+}
+// one value's 16-lane DPP butterfly: the tree oct_sum4 runs on each of its four values
+template <int LPS>
+__device__ __forceinline__ float oct_sum(float x) {
+  x += dpp_row<0xB1>(x);
+  x += dpp_row<0x4E>(x);
+  x += dpp_row<0x141>(x);
+  if constexpr (LPS == 16) x += dpp_row<0x140>(x);
+  return x;
+}
+// the value lane `L` holds, wave-uniform (v_readlane_b32 per 32-bit half, into SGPRs)
+template <int L>
+__device__ __forceinline__ float lane_value(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), L));
+}
+template <int L>
+__device__ __forceinline__ double lane_value(double x) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, x);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, L);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), L);
+  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
+}
+
+// SPLIT: the wave's 64 lanes hold one slot; lane group g computes and reduces row g's dot only
+// (row: its PgsRow) and the four totals are read from lanes 0 / 16 / 32 / 48 into SGPRs for every
+// lane (8 v_readlane_b32 in fp64, 4 in fp32). Each total is the 16-lane slot's, bit for bit: the
+// same FMA chain over the same lanes' dofs and the same DPP tree. The row updates, the force store
+// (one lane of the wave) and v += B'dl (each group's own full copy of v) are the unsplit block's.
+template <typename T, int EPL, int LPS, bool SPLIT = false>
+__device__ __forceinline__ void pgs_block(const PgsBlk<T, EPL>& k, T (&v)[EPL], T* fblk, bool ok0, T& impr,
+                                          const PgsRow<T, EPL>* row = nullptr) {
   typedef typename Vec4T<T>::type V4;
   V4* qf = reinterpret_cast<V4*>(fblk);
   const V4 qb = k.qb, f = k.qf, qR = k.qR, qi = k.qi, qh = k.qh;
   T d0, d1, d2, d3;
-  pgs_dots(k, v, d0, d1, d2, d3);
+  if constexpr (SPLIT) d0 = pgs_row_dot(*row, v);
+  else pgs_dots(k, v, d0, d1, d2, d3);
   // b + R f off the dependent chain
   const T t0 = qb.x + qR.x * f.x, t1 = qb.y + qR.y * f.y;
   const T t2 = qb.z + qR.z * f.z, t3 = qb.w + qR.w * f.w;
-  slot_sum4<LPS>(d0, d1, d2, d3);
+  if constexpr (SPLIT) {
+    const T dg = oct_sum<LPS>(d0);
+    d0 = lane_value<0>(dg); d1 = lane_value<LPS>(dg); d2 = lane_value<2 * LPS>(dg); d3 = lane_value<3 * LPS>(dg);
+  } else {
+    slot_sum4<LPS>(d0, d1, d2, d3);
+  }
   T dl0, dl1, dl2, dl3;
   V4 nfv;
 #define MGX_PGS_ROW(C, I, DOT, DL)                                \
@@ -746,7 +828,7 @@ __device__ __forceinline__ void pgs_block(const PgsBlk<T, EPL>& k, T (&v)[EPL], 
 #undef MGX_PGS_ROW
   // one lane per slot stores the forces: the slot's lanes hold identical values, and a
   // same-address LDS store from every lane serialises
-  if ((lane_id() & (LPS - 1)) == 0) *qf = nfv;
+  if ((lane_id() & ((SPLIT ? 64 : LPS) - 1)) == 0) *qf = nfv;
   pgs_update(k, v, dl0, dl1, dl2, dl3);
 }
 
@@ -763,13 +845,20 @@ __device__ __forceinline__ void pgs_block(const PgsBlk<T, EPL>& k, T (&v)[EPL], 
 // otherwise hold the launch to two waves per CU; bipedal 175.0k -> 186.6k env-steps/s); the
 // soccer launch keeps all scalars in LDS at four waves per CU, which measured faster than the
 // global scalars at any occupancy (MGX_PGS_LDS_PAD sweep).
-template <typename T, int EPL, int LPS, bool BLDS, bool SQG = false, bool DOFB = false>
+// SPLIT (global-B, LPS = 16, all scalars in LDS): every lane of the wave passes the same slot, whose
+// one LDS copy (scalars, forces, table for up to capE = maxE rows) all four lane groups share; in
+// the sweeps lane group g takes row g of each block (pgs_block SPLIT). The warm start and the dual
+// cost stay redundant across the groups; each group keeps its own full copy of v.
+template <typename T, int EPL, int LPS, bool BLDS, bool SQG = false, bool DOFB = false, bool SPLIT = false>
 __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, int capE, int maxit, T tol, T scale,
                                           int spw, int arena = -1) {
   constexpr int RING = BLDS ? MGX_PGS_RING_LDS : MGX_PGS_RING;
   typedef typename Vec4T<T>::type V4;
-  constexpr int SPW = 64 / LPS;
-  const int l = threadIdx.x, s = l / LPS, j = l % LPS;
+  static_assert(!SPLIT || (!BLDS && !SQG && !DOFB && LPS == 16), "row-split mode: the 16-lane global-B solver");
+  constexpr int SPW = SPLIT ? 1 : 64 / LPS;  // slots with LDS of their own
+  constexpr int FL = SPLIT ? 64 : LPS;       // lanes filling one slot's LDS
+  const int l = threadIdx.x, j = l % LPS;
+  const int s = SPLIT ? 0 : l / LPS, fj = SPLIT ? l : j;
   (void)spw;
   const int ne = slot >= 0 ? P.at<int>(P.o_ne)[slot] : 0;  // a multiple of 4
   const int nblk = ne >> 2;
@@ -836,6 +925,8 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
     // LDS capacity in whole ring turns: nbA = capE / 4 rounded up to a multiple of the ring
     const int nbcap = capE / 4;
     nbA = (nbcap + RING - 1) / RING * RING;
+    // a split wave fills only its slot's blocks and the look-ahead (its layout has no second slot)
+    if constexpr (SPLIT) nbA = min(nbA, nbRun + RING - 1);
     const int sstride = (SG ? 4 : 4 * MGX_SCAL) * nbA + 4;  // 16-byte aligned per slot
     sc = reinterpret_cast<T*>(smem) + s * sstride;
     bt = reinterpret_cast<uint32_t*>(reinterpret_cast<T*>(smem) + SPW * sstride) + s * TWL * nbA;
@@ -847,13 +938,13 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
     } else {
       sq = sc;
       fb = sc + MGX_SQ(1, 0);
-      for (int q = j; q < MGX_SCAL * 4 * nbA; q += LPS) sc[q] = q < ne * MGX_SCAL ? gsc[q] : (T)0;
+      for (int q = fj; q < MGX_SCAL * 4 * nbA; q += FL) sc[q] = q < ne * MGX_SCAL ? gsc[q] : (T)0;
     }
   }
   // scalar blocks past the slot's capacity are never real (masked); their loads stay inside it
   const int sbmax = P.maxE / 4 - 1;
   // block table: the slot's blocks, then zero-group entries up to the capacity
-  for (int q = j; q < TWL * nbA; q += LPS) bt[q] = q < TWL * nblk ? (DOFB ? gbt[q] : (uint32_t)gbt16[q]) : 0u;
+  for (int q = fj; q < TWL * nbA; q += FL) bt[q] = q < TWL * nblk ? (DOFB ? gbt[q] : (uint32_t)gbt16[q]) : 0u;
   __syncthreads();
   // warmstart: v = B' f, dual cost, reset to zero if the cost is positive
   T v[EPL];
@@ -891,6 +982,8 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
     for (int d = 0; d < EPL; d++) v[d] = 0;
   }
   __syncthreads();
+  const uint32_t grow = (uint32_t)(l / LPS);  // SPLIT: the lane group's own row of a block
+  (void)grow;
   bool act = ne > 0;
   int it = 0;
 #ifdef MGX_PROFILE
@@ -905,11 +998,13 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
 #endif
     T impr = 0;
     PgsBlk<T, EPL> R[RING];
+    PgsRow<T, EPL> W[RING];  // SPLIT: the lane group's own row of each ring block
     PgsTab<EPL> tn;  // the table entry of the next block to load (one ring step ahead of its data)
     pgs_load_tab<EPL, LPS, DOFB>(tn, bt, 0, j);
 #pragma unroll
     for (int k = 0; k < RING - 1; k++) {
-      pgs_load_block<T, EPL, LPS, FS>(R[k], Bsl, sq, fb, tn, k, min(k, sbmax), j);
+      if constexpr (SPLIT) pgs_load_row(W[k], Bsl, grow, tn);
+      pgs_load_block<T, EPL, LPS, FS, SPLIT>(R[k], Bsl, sq, fb, tn, k, min(k, sbmax), j);
       pgs_load_tab<EPL, LPS, DOFB>(tn, bt, k + 1, j);
     }
     // full ring turns, no early exit inside, so every prefetch is consumed on every path and
@@ -920,9 +1015,10 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
       for (int k = 0; k < RING; k++) {
         // the slot consumed last lands the block RING - 1 ahead, then block b0 + k is solved
         const int bn = min(b0 + k + RING - 1, nbA - 1);
-        pgs_load_block<T, EPL, LPS, FS>(R[(k + RING - 1) % RING], Bsl, sq, fb, tn, bn, min(bn, sbmax), j);
+        if constexpr (SPLIT) pgs_load_row(W[(k + RING - 1) % RING], Bsl, grow, tn);
+        pgs_load_block<T, EPL, LPS, FS, SPLIT>(R[(k + RING - 1) % RING], Bsl, sq, fb, tn, bn, min(bn, sbmax), j);
         pgs_load_tab<EPL, LPS, DOFB>(tn, bt, min(bn + 1, nbA - 1), j);
-        pgs_block<T, EPL, LPS>(R[k], v, fb + FS * (b0 + k), act && b0 + k < nblk, impr);
+        pgs_block<T, EPL, LPS, SPLIT>(R[k], v, fb + FS * (b0 + k), act && b0 + k < nblk, impr, &W[k]);
       }
     }
     if (act) {
@@ -941,7 +1037,7 @@ __device__ __forceinline__ void pgs_group(const Pipe& P, char* smem, int slot, i
     if ((unsigned long long)(nsweep * nbMax) > pr[30]) pr[30] = nsweep * nbMax;
   }
 #endif
-  if (slot >= 0) {
+  if (slot >= 0 && (!SPLIT || l < LPS)) {  // SPLIT: every lane group holds the slot's v; group 0 stores it
     T* vo = P.at<T>(P.o_vout) + (size_t)slot * 64;
 #pragma unroll
     for (int d = 0; d < EPL; d++)
@@ -989,6 +1085,16 @@ __device__ __forceinline__ int sorted_slot(const Pipe& P, int idx, int LPS) {
   }
   return slot;
 }
+// K: the listed slots with at least P.split_blocks blocks, i.e. the first K positions of the
+// heaviest-first order (one more scan of the histogram's top buckets); wave-uniform
+__device__ __forceinline__ int split_count(const Pipe& P) {
+  const int* hist = P.at<int>(P.o_hist);
+  int x = 0;
+  for (int b = P.split_blocks + lane_id(); b < P.nbk; b += 64) x += hist[b];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
+  return __builtin_amdgcn_readfirstlane(x);
+}
 
 template <typename T, int EPL, int LPS, bool BLDS, bool SQG = false, bool DOFB = false>
 __global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T scale, int spw, int big) {
@@ -1002,7 +1108,30 @@ __global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T s
   // main launch and end the step when they trail it: they take their SIMD first
   if (big) __builtin_amdgcn_s_setprio(3);
   const bool dup = big && BLDS;  // the wide LDS-B launch: one slot per wave, every lane group on it
-  for (int base = blockIdx.x * spn; base < cnt; base += gridDim.x * spn) {
+  // Virtual waves, grid-stride (the grid is a capacity bound): the first K take one list position
+  // each in row-split mode, wave w >= K the spn positions from K + spn (w - K) as without the split
+  constexpr bool CAN_SPLIT = !BLDS && !SQG && !DOFB && LPS == 16;
+  int K = 0;
+  if constexpr (CAN_SPLIT) {
+    if (!big && P.split_blocks > 0) K = min(split_count(P), cnt);
+  }
+  const int nw = K + (cnt - K + spn - 1) / spn;
+  for (int w = blockIdx.x; w < nw; w += gridDim.x) {
+    if constexpr (CAN_SPLIT) {
+      if (w < K) {
+        const int slot = __builtin_amdgcn_readfirstlane(sorted_slot(P, w, LPS));
+        const int ne = slot >= 0 ? P.at<int>(P.o_ne)[slot] : 0;
+        // the first waves of the launch, its longest chains: the heavy waves' priority rule
+        const bool hi = ne > P.prio_rows;
+        if (hi) __builtin_amdgcn_s_setprio(3);
+        pgs_group<T, EPL, LPS, false, false, false, true>(P, smem, slot, P.maxE, maxit, tol, scale, spw, -1);
+        if (hi) __builtin_amdgcn_s_setprio(0);
+        if (ne > P.capE && threadIdx.x == 0) atomicAdd(P.ctr() + 6, 1);
+        __syncthreads();
+        continue;
+      }
+    }
+    const int base = K + (w - K) * spn;
     const int idx = dup ? base : (s < spn && base + s < cnt) ? base + s : -1;
     const int slot = big ? (idx >= 0 ? list[idx] : -1) : sorted_slot(P, idx, LPS);
     if constexpr (!BLDS && !SQG) {

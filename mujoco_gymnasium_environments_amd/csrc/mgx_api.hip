@@ -711,6 +711,13 @@ size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks,
     p.o_rk = take(S * p.rk_stride * rb);
     p.o_rks = take(S * 4);
   }
+  // the bank slots' own solver-list state (the bank view of the pipe, MGX_BANK_STREAM) and the
+  // bank finisher's work flags; taken last, so every other offset is what it was without them
+  p.o_ctr2 = take(64);
+  p.o_hist2 = take((size_t)(p.maxE / 4 + 1) * 4);
+  p.o_blist2 = take((size_t)(p.maxE / 4 + 1) * NB * 4);
+  p.o_k2list2 = take(NB * 4); p.o_k2big2 = take(NB * 4);
+  p.o_bstg = take(NB * 4);
   if (P) *P = p;
   return off;
 }
@@ -756,6 +763,13 @@ mgx::Hooks mgx::read_hooks() {
   // more streams than hardware queues (several tasks on one GPU, each on its own stream) a side
   // stream can queue behind another task's long kernels
   h.side_stream = get("MGX_SIDE_STREAM", 1) != 0;
+  // MGX_BANK_STREAM: the soccer reset banks' rows -> PGS -> bank finisher on a library-owned stream
+  // of the lowest priority beside the live step (soccer_step_staged); 1: the bank finisher before
+  // the live finisher, 2: after it; 0: one stream. MGX_SIDE_STREAM=0 turns it off as well.
+  // Not set (-1): MGX_BANK_STREAM (mgx_staged.h) in fp64; off in fp32, where it measured 2% slower
+  // (the fp32 solver launch is shorter, so its idle tail holds less than the sharing costs).
+  h.bank_stream = get("MGX_BANK_STREAM", -1);
+  if (h.bank_stream < -1 || h.bank_stream > 2) h.bank_stream = 0;
   h.gcon = get("MGX_GCON", 1);
   h.rows_lds = get("MGX_ROWS_LDS", 0);
   return h;
@@ -787,6 +801,47 @@ static SideStream* side_stream(hipStream_t st) {
   return x;
 }
 
+// The bank pipeline's stream (MGX_BANK_STREAM) and its events per caller stream, created once and
+// kept for the process: the lowest stream priority the device offers, so the live step's waves are
+// dispatched first. nullptr if the runtime refuses (then the step runs on one stream).
+struct BankStream {
+  hipStream_t s;
+  hipEvent_t entry, rows, live, done;
+};
+static BankStream* bank_stream(hipStream_t st) {
+  static std::mutex mu;
+  static std::map<std::pair<hipStream_t, int>, BankStream*> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  auto key = std::make_pair(st, dev);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  BankStream* x = new BankStream{};
+  int least = 0, greatest = 0;
+  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
+      hipStreamCreateWithPriority(&x->s, hipStreamNonBlocking, least) != hipSuccess ||
+      hipEventCreateWithFlags(&x->entry, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x->rows, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x->live, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&x->done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    delete x;
+    x = nullptr;
+  }
+  cache[key] = x;
+  return x;
+}
+// The bank view of a pipe: the bank slots' own solver-list state (Pipe, mgx_staged.h); no bank
+// wave raises its priority
+static Pipe bank_view(const Pipe& P) {
+  Pipe B = P;
+  B.o_ctr = P.o_ctr2; B.o_hist = P.o_hist2; B.o_blist = P.o_blist2; B.o_k2list = P.o_k2list2; B.o_k2big = P.o_k2big2;
+  B.S = P.N * (P.R > 0 ? P.R : 1);
+  B.prio_rows = P.maxE;
+  return B;
+}
+
 // LDS of the one-wave settle: the row builder's layout, then one solver wave with maxE rows per
 // slot, then the finisher's layout, in turn
 static int settle_lds_bytes(const mgx_model* m, const Pipe& P) {
@@ -810,8 +865,66 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   const Hooks& H = m->hooks;
   // occupancy probe: MGX_ROWS_LDS pads the row builder's LDS (fewer waves per CU; up to 64 KiB)
   const int rlds = H.rows_lds > m->Ls.bytes && H.rows_lds <= 64 * 1024 ? H.rows_lds : m->Ls.bytes;
-  launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, banks, slots, rlds, st);
   T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+  // The bank pipeline (MGX_BANK_STREAM): the bank slots are not needed by this step and their
+  // chains are short, while the live envs' longest chain sets the solver launch's length and
+  // leaves most of the GPU idle at its end. So the bank slots' rows -> PGS -> bank finisher run on
+  // their own lowest-priority stream, over the bank view of the pipe, beside the live launches:
+  //
+  //   caller:  E  rows(live) -> PGS(live) ---------> [1: wait D] finish -> fixup -> L  [2: wait D]
+  //   bank:    wait E  rows(bank) -> R -> PGS(bank) -> [2: wait L] bank finish -> D
+  //
+  // E orders the bank stream behind the previous call's bank_install and reset(). Mode 1: a bank
+  // completing its tenth step is ready for this step's resets, as on one stream. Mode 2: the bank
+  // finisher follows the live finisher and the fixup (both restart bank records, which the bank
+  // finisher must not be writing meanwhile; it then skips the restarted records, o_bstg), so a bank
+  // is ready one step later and only the bank finisher is left on the live path; the live finisher
+  // waits for R, because the bank row builder reads the records it restarts. Either way the call
+  // returns with the caller's stream behind all bank work (the workspace is the caller's).
+  // Readiness depends on step counts only, and a reset is the same bits whether its bank was
+  // ready or not, so no mode changes a result. Needs the one-launch solver (no wide launch).
+  int bmode = banks > 0 && H.side_stream && !H.pgs_lds_b && !H.pgs_single &&
+                      (P.maxE <= P.capE || P.hmain || P.split_blocks)
+                  ? (H.bank_stream >= 0 ? H.bank_stream : m->precision == MGX_F32 ? 0 : MGX_BANK_STREAM) : 0;
+  BankStream* bs = bmode ? bank_stream(st) : nullptr;
+  if (bs) {
+    const Pipe B = bank_view(P);
+    const int nbank = n_env * P.R;
+    // with the bank waves beside them, all the row-split waves (the launch's long chains) take
+    // their SIMD first; MGX_PGS_PRIO_ROWS sets the threshold for A/B runs
+    if (!H.pgs_prio_rows && P.split_blocks) P.prio_rows = 4 * P.split_blocks - 1;
+    int mlds = pgs_lds_bytes(m, P.capE, P.sqg);
+    if (P.hmain) mlds = std::max(mlds, pgs_lds_bytes(m, P.maxE, 1));
+    if (P.split_blocks) mlds = std::max(mlds, staged_pgs_lds_bytes(m, P.maxE, 64, 0, mgx_twl(false)));
+    if (H.pgs_lds_pad > mlds && H.pgs_lds_pad <= 96 * 1024) mlds = H.pgs_lds_pad;
+    HIPCHK(hipEventRecord(bs->entry, st));
+    launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, 0, n_env, rlds, st);
+    HIPCHK(hipStreamWaitEvent(bs->s, bs->entry, 0));
+    launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, nullptr, B, banks, nbank, rlds, bs->s, n_env);
+    if (bmode == 2) HIPCHK(hipEventRecord(bs->rows, bs->s));
+    launch_pgs<T>(B, nbank, mlds, bs->s, M.iterations, M.tolerance, scale, 0, H);
+    if (bmode == 1) {
+      launch_soccer_bank_finish<T>(Mf, ids, n_env, B, 1, m->Lf.bytes, bs->s);
+      HIPCHK(hipEventRecord(bs->done, bs->s));
+    }
+    launch_pgs<T>(P, n_env, mlds, st, M.iterations, M.tolerance, scale, 0, H);
+    HIPCHK(hipStreamWaitEvent(st, bmode == 1 ? bs->done : bs->rows, 0));
+    launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
+                            env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false);
+    int fgrid = n_env < 256 ? n_env : 256;
+    launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
+                            SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
+    if (bmode == 2) {
+      HIPCHK(hipEventRecord(bs->live, st));
+      HIPCHK(hipStreamWaitEvent(bs->s, bs->live, 0));
+      launch_soccer_bank_finish<T>(Mf, ids, n_env, B, 1, m->Lf.bytes, bs->s);
+      HIPCHK(hipEventRecord(bs->done, bs->s));
+      HIPCHK(hipStreamWaitEvent(st, bs->done, 0));
+    }
+    HIPCHK(hipGetLastError());
+    return MGX_OK;
+  }
+  launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, banks, slots, rlds, st);
   // slots over the main launch's LDS rows (MuJoCo has no cap: the rows are kept, not dropped):
   // a small grid-stride global-B launch with maxE rows of LDS per slot, which exits at once when
   // the list is empty. It runs on a side stream beside the main launch (a slot of ~300 rows is
@@ -1133,9 +1246,11 @@ int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_
   if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
   Pipe P;
   make_pipe(m, nullptr, n_env, banks, &P);
-  const int64_t v[11] = {(int64_t)P.o_ctr, (int64_t)P.o_ne, (int64_t)P.o_k2list, (int64_t)P.o_blk, (int64_t)P.o_B,
-                         P.bcap, P.maxE, P.capE, P.S, m->precision == MGX_F32 ? 4 : 8, (int64_t)P.o_k2big};
-  for (int i = 0; i < (n_out < 11 ? n_out : 11); i++) out[i] = v[i];
+  // [11], [12]: the bank view's counter block and arrival list (MGX_BANK_STREAM)
+  const int64_t v[13] = {(int64_t)P.o_ctr, (int64_t)P.o_ne, (int64_t)P.o_k2list, (int64_t)P.o_blk, (int64_t)P.o_B,
+                         P.bcap, P.maxE, P.capE, P.S, m->precision == MGX_F32 ? 4 : 8, (int64_t)P.o_k2big,
+                         (int64_t)P.o_ctr2, (int64_t)P.o_k2list2};
+  for (int i = 0; i < (n_out < 13 ? n_out : 13); i++) out[i] = v[i];
   return MGX_OK;
 }
 

@@ -35,6 +35,9 @@ struct Hooks {
                               // one slot per wave (-1: the pipeline's default; 0: off; 1: every slot)
   int tight_bp = -1;    // MGX_TIGHT_BROADPHASE: box prefilters in the broadphase (-1: by the pair count)
   int side_stream = 1;   // MGX_SIDE_STREAM: the wide solver launch on a side stream
+  int bank_stream = 0;   // MGX_BANK_STREAM: the soccer reset banks' pipeline on a low-priority stream beside the
+                         // live step (0: off, one stream; 1: bank finisher before the live one; 2: after it;
+                         // -1, not set: the compiled default MGX_BANK_STREAM in fp64, off in fp32)
   int gcon = 1;          // MGX_GCON: the row builder's contact points in the pipe (0: in LDS)
   int rows_lds = 0;      // MGX_ROWS_LDS: pad the row builder's LDS (occupancy probe)
 };
@@ -117,12 +120,15 @@ int pgs_configure_lds(int precision, int bytes, int wide);
 template <typename T>
 void launch_soccer_rows(const DevModel<T>& Ms, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                         const float* action, int n_env, const uint8_t* mask, const Pipe& P, int banks, int slots, int lds,
-                        hipStream_t st);
+                        hipStream_t st, int slot0 = 0);
+template <typename T>
+void launch_soccer_bank_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, int n_env, const Pipe& P, int lists,
+                               int lds, hipStream_t st);
 template <typename T>
 void launch_soccer_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                           const float* action, float* obs, double* reward, uint8_t* terminated, uint8_t* truncated,
                           float* final_obs, int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask,
-                          const Pipe& P, int banks, int lds, hipStream_t st);
+                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too = true);
 template <typename T>
 void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s,
                           const mgx_soccer_env& ev, const T* draws, float* obs, uint64_t seed, int env_offset, int n_env,

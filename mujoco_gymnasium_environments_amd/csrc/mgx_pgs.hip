@@ -70,9 +70,10 @@ template void launch_pgs<double>(const Pipe&, int, int, hipStream_t, int, double
 template <typename T>
 __global__ void __launch_bounds__(64) k_soccer_rows(DevModel<T> m, SoccerIds<T> ids, mgx_state s, mgx_soccer_env ev,
                                                     const float* action, int n_env, const uint8_t* mask, Pipe P,
-                                                    int banks) {
+                                                    int banks, int b0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int b = blockIdx.x;
+  // b0: the launch's first slot (0; n_env for the bank pipeline's launch over the bank slots only)
+  int b = b0 + blockIdx.x;
   int slot;
   Env<T> e;
   if (b < n_env) {
@@ -88,7 +89,9 @@ __global__ void __launch_bounds__(64) k_soccer_rows(DevModel<T> m, SoccerIds<T> 
     int bi = b - n_env;
     if (!banks || bi >= n_env * P.R) return;
     int k = P.at<int>(P.o_bk)[bi];
-    if (k < 0 || k >= 10) return;
+    const bool run = k >= 0 && k < 10;
+    if (lane_id() == 0) P.at<int>(P.o_bstg)[bi] = run;  // the bank finisher's work list
+    if (!run) return;
     env_bind(m, e, smem);
     bind_carry_tail(m, e, P, b);
     bank_load_state(m, e, P, bi);
@@ -102,14 +105,28 @@ __global__ void __launch_bounds__(64) k_soccer_rows(DevModel<T> m, SoccerIds<T> 
 
 // The bank slots' settle steps (S3 of the extra slots), one wave per bank record, launched before
 // the live finisher: a bank that completes its tenth step here is ready for a reset in this
-// step's live finisher, as when one wave finished an env's banks and then the env.
+// step's live finisher, as when one wave finished an env's banks and then the env. On the bank
+// stream (MGX_BANK_STREAM) it may also run after the live finisher and the fixup: it advances the
+// records whose rows this step's row builder staged (o_bstg), so a record restarted in between
+// (bank_install, the fixup) waits for its first rows. lists: P is the bank view, whose consumed
+// solver lists are reset here as the live finisher resets the live view's.
 template <typename T>
-__global__ void __launch_bounds__(64) k_soccer_bank_finish(DevModel<T> m, SoccerIds<T> ids, int n_env, Pipe P) {
+__global__ void __launch_bounds__(64) k_soccer_bank_finish(DevModel<T> m, SoccerIds<T> ids, int n_env, Pipe P,
+                                                           int lists) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int bi = blockIdx.x;
+  if (lists && bi == 0) {
+    if (lane_id() == 0) {
+      P.ctr()[3] = P.ctr()[1];
+      P.ctr()[4] = P.ctr()[2];
+      P.ctr()[1] = 0;
+      P.ctr()[2] = 0;
+    }
+    for (int b = lane_id(); b < P.nbk; b += 64) P.at<int>(P.o_hist)[b] = 0;
+  }
   if (bi >= n_env * P.R) return;
+  if (!P.at<int>(P.o_bstg)[bi]) return;
   int k = P.at<int>(P.o_bk)[bi];
-  if (k < 0 || k >= 10) return;
   Env<T> e;
   env_bind(m, e, smem);
   const int slot = n_env + bi;
@@ -121,7 +138,10 @@ __global__ void __launch_bounds__(64) k_soccer_bank_finish(DevModel<T> m, Soccer
   bank_store_state(m, e, P, bi, warn);
   k++;
   if (k == 10) bank_finalize(m, e, ids, P, bi);
-  if (lane_id() == 0) P.at<int>(P.o_bk)[bi] = k;
+  if (lane_id() == 0) {
+    P.at<int>(P.o_bk)[bi] = k;
+    P.at<int>(P.o_bstg)[bi] = 0;
+  }
 }
 
 template <typename T>
@@ -188,16 +208,23 @@ __global__ void __launch_bounds__(64) k_soccer_finish(DevModel<T> m, SoccerIds<T
 template <typename T>
 void launch_soccer_rows(const DevModel<T>& Ms, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                         const float* action, int n_env, const uint8_t* mask, const Pipe& P, int banks, int slots, int lds,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(k_soccer_rows<T>, dim3(slots), dim3(64), lds, st, Ms, ids, s, ev, action, n_env, mask, P, banks);
+                        hipStream_t st, int slot0) {
+  hipLaunchKernelGGL(k_soccer_rows<T>, dim3(slots), dim3(64), lds, st, Ms, ids, s, ev, action, n_env, mask, P, banks,
+                     slot0);
 }
+// lists: P is the bank view of the pipe (the bank pipeline's launch), whose solver lists it resets
+template <typename T>
+void launch_soccer_bank_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, int n_env, const Pipe& P, int lists,
+                               int lds, hipStream_t st) {
+  hipLaunchKernelGGL(k_soccer_bank_finish<T>, dim3(n_env * P.R), dim3(64), lds, st, Mf, ids, n_env, P, lists);
+}
+// bank_too: the bank slots' finisher first, on the same stream (the single-stream step)
 template <typename T>
 void launch_soccer_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                           const float* action, float* obs, double* reward, uint8_t* terminated, uint8_t* truncated,
                           float* final_obs, int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask,
-                          const Pipe& P, int banks, int lds, hipStream_t st) {
-  if (banks && P.R > 0)
-    hipLaunchKernelGGL(k_soccer_bank_finish<T>, dim3(n_env * P.R), dim3(64), lds, st, Mf, ids, n_env, P);
+                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too) {
+  if (bank_too && banks && P.R > 0) launch_soccer_bank_finish<T>(Mf, ids, n_env, P, 0, lds, st);
   hipLaunchKernelGGL(k_soccer_finish<T>, dim3(n_env), dim3(64), lds, st, Mf, ids, s, ev, action, obs, reward, terminated,
                      truncated, final_obs, autoreset, seed, env_offset, n_env, mask, P, banks);
 }
@@ -225,10 +252,13 @@ void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const So
 }
 #define MGX_STAGED_INST(T)                                                                                              \
   template void launch_soccer_rows<T>(const DevModel<T>&, const SoccerIds<T>&, const mgx_state&, const mgx_soccer_env&, \
-                                      const float*, int, const uint8_t*, const Pipe&, int, int, int, hipStream_t);      \
+                                      const float*, int, const uint8_t*, const Pipe&, int, int, int, hipStream_t, int); \
+  template void launch_soccer_bank_finish<T>(const DevModel<T>&, const SoccerIds<T>&, int, const Pipe&, int, int,       \
+                                             hipStream_t);                                                              \
   template void launch_soccer_finish<T>(const DevModel<T>&, const SoccerIds<T>&, const mgx_state&,                      \
                                         const mgx_soccer_env&, const float*, float*, double*, uint8_t*, uint8_t*, float*, \
-                                        int, uint64_t, int, int, const uint8_t*, const Pipe&, int, int, hipStream_t);     \
+                                        int, uint64_t, int, int, const uint8_t*, const Pipe&, int, int, hipStream_t,      \
+                                        bool);                                                                            \
   template void launch_soccer_settle<T>(const DevModel<T>&, const DevModel<T>&, const SoccerIds<T>&, const mgx_state&, \
                                         const mgx_soccer_env&, const T*, float*, uint64_t, int, int, const uint8_t*,    \
                                         const Pipe&, int, int, int, hipStream_t, int, T, T);

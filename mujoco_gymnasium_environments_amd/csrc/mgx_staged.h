@@ -47,7 +47,8 @@ __host__ __device__ constexpr int mgx_twl(bool dofb) { return dofb ? 4 : 8; }  /
 #define MGX_PGS_RING_LDS 2     // LDS-B solver: one block in flight covers the LDS latency
 #define MGX_PGS_LDS_ROWS 192   // rows per slot the main solver launch keeps in LDS (2 waves / CU in fp64)
 #define MGX_PGS_SPLIT_BLOCKS 40  // soccer main launch: slots of at least this many blocks are solved row-split, one per wave
-#define MGX_PGS_WIDE_GRID 256  // waves of the global-B launch (slots over MGX_PGS_LDS_ROWS, waves over their arena)
+#define MGX_BANK_STREAM 1      // soccer: the reset banks' pipeline on its own stream (0: off; 1 / 2: soccer_step_staged)
+#define MGX_PGS_WIDE_GRID 256 // waves of the global-B launch (slots over MGX_PGS_LDS_ROWS, waves over their arena)
 #define MGX_PGS_WIDE_LDS_GRID 32  // waves of the wide launch with LDS-resident B (one slot per wave)
 #define MGX_PGS_ARENA_F64 49152  // LDS arena per main-launch solver wave of 4 slots, fp64 (tools/pgs_census.py)
 #define MGX_PGS_ARENA_F32 32768  //                                                    fp32
@@ -98,6 +99,15 @@ struct Pipe {
   // kernel's row scratch (monolithic layout with rows in global memory)
   int rk_stride;
   size_t o_rk, o_rks, o_rkw, o_tscr;
+  // The soccer bank pipeline (a second stream beside the live step, MGX_BANK_STREAM): the bank
+  // slots' own solver-list state — counter block, histogram, bucket list with stride N * R, arrival
+  // lists. The "bank view" of a pipe is a copy whose o_ctr, o_hist, o_blist, o_k2list, o_k2big and
+  // S name this state (mgx_api.hip: bank_view); all per-slot storage keeps its global slot index, so
+  // the row builder, sorted_slot, split_count and k_pgs_groups run on either view.
+  // o_bstg: per bank record, 1 while the record's rows of this step are staged and its settle step
+  // is still to be finished (the row builder sets it, a restart of the record clears it): the bank
+  // finisher advances exactly the records whose rows were built, wherever it sits in the step.
+  size_t o_ctr2, o_hist2, o_blist2, o_k2list2, o_k2big2, o_bstg;
   template <typename X> __device__ __forceinline__ X* at(size_t off) const { return reinterpret_cast<X*>(base + off); }
   // [0] fixup count, [1] solver-list count, [2] wide-solver-list count, [3] / [4] the last
   // step's list sizes, [5] RK4 step: fixup count (k_pgs_groups clears [0] at every launch),
@@ -1099,7 +1109,9 @@ __device__ __forceinline__ int split_count(const Pipe& P) {
 template <typename T, int EPL, int LPS, bool BLDS, bool SQG = false, bool DOFB = false>
 __global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T scale, int spw, int big) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (!big && blockIdx.x == 0 && threadIdx.x == 0) P.ctr()[0] = 0;  // fixup list count, filled by the finisher
+  // fixup list count, filled by the finisher (the live view's; on the bank view this word of its
+  // own counter block is unused)
+  if (!big && blockIdx.x == 0 && threadIdx.x == 0) P.ctr()[0] = 0;
   const int cnt = P.ctr()[big ? 2 : 1];
   const int* list = P.at<int>(P.o_k2big);
   const int spn = spw < 0 ? -spw : spw;
@@ -1262,6 +1274,7 @@ __device__ __forceinline__ void bank_init_draws(const DevModel<T>& m, Env<T>& e,
     P.at<int>(P.o_bep)[bi] = episode;
     P.at<uint64_t>(P.o_bseed)[bi] = seed;
     P.at<int>(P.o_bk)[bi] = 0;
+    P.at<int>(P.o_bstg)[bi] = 0;  // rows staged for the record's earlier state are void
   }
   wsync();
 }

@@ -449,6 +449,8 @@ int build_model(const mgx_model_desc* d, int device, mgx_model* out, DevModel<T>
   M.iterations = d->iterations;
   M.timestep = (T)d->timestep; M.tolerance = (T)d->tolerance; M.impratio = (T)d->impratio;
   M.meaninertia = (T)d->meaninertia;
+  M.has_damping = 0;  // any dof_damping > 0 at the model's precision: Euler integrates implicitly in velocity
+  for (int k = 0; k < nv; k++) M.has_damping |= (T)d->dof_damping[k] > (T)0;
   for (int k = 0; k < 3; k++) M.gravity[k] = (T)d->gravity[k];
   // derived tables: body chains, dof ancestors
   std::vector<int> chain(nb * MGX_MAX_DEPTH, 0), depth(nb, 0);
@@ -718,6 +720,9 @@ size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks,
   p.o_blist2 = take((size_t)(p.maxE / 4 + 1) * NB * 4);
   p.o_k2list2 = take(NB * 4); p.o_k2big2 = take(NB * 4);
   p.o_bstg = take(NB * 4);
+  // the tail finisher's deferred resets (MGX_TAIL_FINISH): a count, then up to N envs
+  p.o_defer = take(((size_t)n_env + 1) * 4);
+  p.qmh_pre = 0;  // set per step by soccer_step_staged
   if (P) *P = p;
   return off;
 }
@@ -766,10 +771,22 @@ mgx::Hooks mgx::read_hooks() {
   // MGX_BANK_STREAM: the soccer reset banks' rows -> PGS -> bank finisher on a library-owned stream
   // of the lowest priority beside the live step (soccer_step_staged); 1: the bank finisher before
   // the live finisher, 2: after it; 0: one stream. MGX_SIDE_STREAM=0 turns it off as well.
-  // Not set (-1): MGX_BANK_STREAM (mgx_staged.h) in fp64; off in fp32, where it measured 2% slower
-  // (the fp32 solver launch is shorter, so its idle tail holds less than the sharing costs).
+  // Not set (-1): MGX_BANK_STREAM (mgx_staged.h); in fp32 only together with the tail finisher
+  // (MGX_TAIL_FINISH), without which it measured 2% slower there (the fp32 solver launch is
+  // shorter, so its idle tail holds less than the sharing costs).
   h.bank_stream = get("MGX_BANK_STREAM", -1);
   if (h.bank_stream < -1 || h.bank_stream > 2) h.bank_stream = 0;
+  // MGX_TAIL_FINISH: the soccer step's row-split (heavy) solver waves on a side stream, the light
+  // envs finished on the caller's stream beside them and the heavy envs after them
+  // (soccer_step_staged). Off wherever the side stream is (MGX_SIDE_STREAM=0, MGX_PGS_LDS_B,
+  // MGX_PGS_SINGLE) and without row-split waves. Not set (-1): MGX_TAIL_FINISH (mgx_staged.h)
+  // beside the bank stream, off on one stream (where only 1 turns it on).
+  h.tail_finish = get("MGX_TAIL_FINISH", -1);
+  if (h.tail_finish < -1 || h.tail_finish > 1) h.tail_finish = 0;
+  // MGX_TAIL_FACTOR (with the tail finisher): 1 the row builder factorises qMH for the heavy slots,
+  // whose finish ends the step (Pipe.qmh_pre); 0 never; 2 for every slot (test hook)
+  h.tail_factor = get("MGX_TAIL_FACTOR", 1);
+  if (h.tail_factor < 0 || h.tail_factor > 2) h.tail_factor = 1;
   h.gcon = get("MGX_GCON", 1);
   h.rows_lds = get("MGX_ROWS_LDS", 0);
   return h;
@@ -839,6 +856,7 @@ static Pipe bank_view(const Pipe& P) {
   B.o_ctr = P.o_ctr2; B.o_hist = P.o_hist2; B.o_blist = P.o_blist2; B.o_k2list = P.o_k2list2; B.o_k2big = P.o_k2big2;
   B.S = P.N * (P.R > 0 ? P.R : 1);
   B.prio_rows = P.maxE;
+  B.qmh_pre = 0;  // bank records end no step
   return B;
 }
 
@@ -883,10 +901,36 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   // returns with the caller's stream behind all bank work (the workspace is the caller's).
   // Readiness depends on step counts only, and a reset is the same bits whether its bank was
   // ready or not, so no mode changes a result. Needs the one-launch solver (no wide launch).
+  // the tail finisher (below) can run, and is on unless MGX_TAIL_FINISH=0
+  const bool tail_on = (H.tail_finish >= 0 ? H.tail_finish : MGX_TAIL_FINISH) && H.side_stream && !H.pgs_lds_b &&
+                       !H.pgs_single && P.split_blocks > 0;
+  // MGX_BANK_STREAM not set: on in fp64; in fp32 on with the tail finisher only (alone it measured
+  // 2% slower there, with the tail finisher 6% faster than one stream)
   int bmode = banks > 0 && H.side_stream && !H.pgs_lds_b && !H.pgs_single &&
                       (P.maxE <= P.capE || P.hmain || P.split_blocks)
-                  ? (H.bank_stream >= 0 ? H.bank_stream : m->precision == MGX_F32 ? 0 : MGX_BANK_STREAM) : 0;
+                  ? (H.bank_stream >= 0 ? H.bank_stream : m->precision == MGX_F32 && !tail_on ? 0 : MGX_BANK_STREAM) : 0;
   BankStream* bs = bmode ? bank_stream(st) : nullptr;
+  // The tail finisher (MGX_TAIL_FINISH): the solver launch is as long as its heaviest slot's chain,
+  // and an env's finish needs only that env's solver result. So the launch is split at the
+  // row-split threshold: the heavy slots' waves (one slot each, K of them) go to a side stream
+  // behind event H, the bulk stays on the caller's stream, and the finisher runs in two tiers:
+  //
+  //   caller:  E  rows(live) H -> PGS(bulk) -> finish A ------> [wait V, 1: D, 2: R] finish B -> fixup -> L
+  //   side:    wait H  PGS(heavy) -> V
+  //   bank:    wait E  rows(bank) -> R -> PGS(bank) -> [2: wait L] bank finish -> D
+  //
+  // Tier A finishes the light envs beside the heavy chains. It restarts no bank record and leaves
+  // the solver lists alone (the heavy launch reads them): an env that ended its episode is put on
+  // the deferred list, so tier A is ordered against nothing but the bulk launch. Tier B finishes the
+  // heavy envs, installs the deferred resets and clears the lists; it sits where the one finisher
+  // sat (behind D or R), so bank records are restarted exactly where they were and the ordering
+  // above holds. Each env's finish is the same code on the same inputs in either tier.
+  // Without the bank stream the bank slots share the one solver list: the bank finisher then
+  // follows V, before tier B; that layout measured 10% slower than the one launch (fp32), so it
+  // runs only when MGX_TAIL_FINISH=1 asks for it.
+  SideStream* tail = tail_on && (bs || H.tail_finish == 1) ? side_stream(st) : nullptr;
+  // tier B's waves are the step's last: the row builder takes euler()'s qMH factorisation off them
+  if (tail) P.qmh_pre = H.tail_factor;
   if (bs) {
     const Pipe B = bank_view(P);
     const int nbank = n_env * P.R;
@@ -899,6 +943,12 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
     if (H.pgs_lds_pad > mlds && H.pgs_lds_pad <= 96 * 1024) mlds = H.pgs_lds_pad;
     HIPCHK(hipEventRecord(bs->entry, st));
     launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, 0, n_env, rlds, st);
+    if (tail) {
+      HIPCHK(hipEventRecord(tail->rows, st));
+      HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
+      launch_pgs<T>(P, n_env, mlds, tail->s, M.iterations, M.tolerance, scale, 0, H, 1);
+      HIPCHK(hipEventRecord(tail->big, tail->s));
+    }
     HIPCHK(hipStreamWaitEvent(bs->s, bs->entry, 0));
     launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, nullptr, B, banks, nbank, rlds, bs->s, n_env);
     if (bmode == 2) HIPCHK(hipEventRecord(bs->rows, bs->s));
@@ -907,10 +957,15 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
       launch_soccer_bank_finish<T>(Mf, ids, n_env, B, 1, m->Lf.bytes, bs->s);
       HIPCHK(hipEventRecord(bs->done, bs->s));
     }
-    launch_pgs<T>(P, n_env, mlds, st, M.iterations, M.tolerance, scale, 0, H);
+    launch_pgs<T>(P, n_env, mlds, st, M.iterations, M.tolerance, scale, 0, H, tail ? 2 : 0);
+    if (tail) {
+      launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
+                              env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, 1);
+      HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
+    }
     HIPCHK(hipStreamWaitEvent(st, bmode == 1 ? bs->done : bs->rows, 0));
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                            env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false);
+                            env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, tail ? 2 : 0);
     int fgrid = n_env < 256 ? n_env : 256;
     launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
                             SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
@@ -938,6 +993,25 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   if (P.split_blocks) mlds = std::max(mlds, staged_pgs_lds_bytes(m, P.maxE, 64, 0, mgx_twl(false)));
   // occupancy probe: MGX_PGS_LDS_PAD pads the main solver launch's LDS (fewer waves per CU)
   if (H.pgs_lds_pad > mlds && H.pgs_lds_pad <= 96 * 1024) mlds = H.pgs_lds_pad;
+  if (tail) {
+    // the tail finisher on one solver list (live and bank slots): the heavy slots of either kind on
+    // the side stream, tier A beside them, then the bank finisher and tier B
+    HIPCHK(hipEventRecord(tail->rows, st));
+    HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
+    launch_pgs<T>(P, slots, mlds, tail->s, M.iterations, M.tolerance, scale, 0, H, 1);
+    HIPCHK(hipEventRecord(tail->big, tail->s));
+    launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H, 2);
+    launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
+                            env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, 1);
+    HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
+    launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
+                            env_offset, n_env, mask, P, banks, m->Lf.bytes, st, true, 2);
+    int fgrid = n_env < 256 ? n_env : 256;
+    launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
+                            SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
+    HIPCHK(hipGetLastError());
+    return MGX_OK;
+  }
   if (!H.pgs_lds_b && (P.maxE <= P.capE || P.hmain || P.split_blocks)) {
     // every slot fits the main launch (the default capacity): no wide launch at all
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H);
@@ -1246,11 +1320,12 @@ int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_
   if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
   Pipe P;
   make_pipe(m, nullptr, n_env, banks, &P);
-  // [11], [12]: the bank view's counter block and arrival list (MGX_BANK_STREAM)
-  const int64_t v[13] = {(int64_t)P.o_ctr, (int64_t)P.o_ne, (int64_t)P.o_k2list, (int64_t)P.o_blk, (int64_t)P.o_B,
+  // [11], [12]: the bank view's counter block and arrival list (MGX_BANK_STREAM); [13], [14]: the
+  // deferred-reset list and the row-split threshold in blocks (MGX_TAIL_FINISH)
+  const int64_t v[15] = {(int64_t)P.o_ctr, (int64_t)P.o_ne, (int64_t)P.o_k2list, (int64_t)P.o_blk, (int64_t)P.o_B,
                          P.bcap, P.maxE, P.capE, P.S, m->precision == MGX_F32 ? 4 : 8, (int64_t)P.o_k2big,
-                         (int64_t)P.o_ctr2, (int64_t)P.o_k2list2};
-  for (int i = 0; i < (n_out < 13 ? n_out : 13); i++) out[i] = v[i];
+                         (int64_t)P.o_ctr2, (int64_t)P.o_k2list2, (int64_t)P.o_defer, P.split_blocks};
+  for (int i = 0; i < (n_out < 15 ? n_out : 15); i++) out[i] = v[i];
   return MGX_OK;
 }
 

@@ -94,6 +94,7 @@ template <typename T>
 struct DevModel {
   int nq, nv, nu, nbody, njnt, ngeom, npair, nM, nmaskword;
   int solver, integrator, cone, iterations;
+  int has_damping;  // some dof_damping > 0 (euler)
   T timestep, tolerance, impratio, meaninertia, gravity[3];
   // bodies
   const int *body_parentid, *body_rootid, *body_jntnum, *body_jntadr, *body_dofnum, *body_dofadr;

@@ -37,7 +37,12 @@ struct Hooks {
   int side_stream = 1;   // MGX_SIDE_STREAM: the wide solver launch on a side stream
   int bank_stream = 0;   // MGX_BANK_STREAM: the soccer reset banks' pipeline on a low-priority stream beside the
                          // live step (0: off, one stream; 1: bank finisher before the live one; 2: after it;
-                         // -1, not set: the compiled default MGX_BANK_STREAM in fp64, off in fp32)
+                         // -1, not set: the compiled default MGX_BANK_STREAM; in fp32 only with the tail finisher)
+  int tail_finish = -1;  // MGX_TAIL_FINISH: soccer: the row-split (heavy) slots' solver waves on a side stream and
+                         // the light envs finished beside them (soccer_step_staged; 0: off; 1: on;
+                         // -1, not set: the compiled default MGX_TAIL_FINISH beside the bank stream, off without it)
+  int tail_factor = 1;   // MGX_TAIL_FACTOR: with the tail finisher, the row builder factorises qMH for the heavy
+                         // slots (1), for no slot (0), for every slot (2: test hook)
   int gcon = 1;          // MGX_GCON: the row builder's contact points in the pipe (0: in LDS)
   int rows_lds = 0;      // MGX_ROWS_LDS: pad the row builder's LDS (occupancy probe)
 };
@@ -113,7 +118,8 @@ int host_check_state(const mgx_state* s);
 int step_kernels_configure(const mgx_model* m);
 // the staged solver S2 (mgx_pgs.hip)
 template <typename T>
-void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big, const Hooks& h);
+void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big, const Hooks& h,
+                int part = 0);
 // bytes: the solver kernels' dynamic-LDS limit; wide: the LDS-B instantiations' (the wide launch)
 int pgs_configure_lds(int precision, int bytes, int wide);
 // S1 / S3 and the one-wave settle (mgx_pgs.hip, the staged TU)
@@ -128,7 +134,7 @@ template <typename T>
 void launch_soccer_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                           const float* action, float* obs, double* reward, uint8_t* terminated, uint8_t* truncated,
                           float* final_obs, int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask,
-                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too = true);
+                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too = true, int tier = 0);
 template <typename T>
 void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s,
                           const mgx_soccer_env& ev, const T* draws, float* obs, uint64_t seed, int env_offset, int n_env,

@@ -25,14 +25,16 @@ int pgs_lanes() {
 }
 template <typename T, int LPS, bool BLDS, bool SQG = false>
 static void launch_lps(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big,
-                       int spw_hook, int spw_force = 0) {
+                       int spw_hook, int spw_force = 0, int part = 0) {
   const int spw = spw_force ? spw_force : spw_hook ? spw_hook : 64 / LPS;  // spw_hook: MGX_PGS_SPW (debug)
   int grid = (slots + (spw < 0 ? -spw : spw) - 1) / (spw < 0 ? -spw : spw);
+  // the heavy launch (part 1): one row-split slot per wave, grid-stride; surplus waves exit
+  if (part == 1) grid = slots < MGX_TAIL_HEAVY_GRID ? slots : MGX_TAIL_HEAVY_GRID;
   switch ((P.dpl + LPS / 8 - 1) / (LPS / 8)) {  // register entries per lane
 #define MGX_PGS_CASE(E)                                                                                          \
     case E:                                                                                                     \
       hipLaunchKernelGGL((k_pgs_groups<T, E, LPS, BLDS, SQG>), dim3(grid), dim3(64), lds, st, P, maxit, tol, scale, spw, \
-                         big);                                                                                  \
+                         big, part);                                                                            \
       break;
     MGX_PGS_CASE(1)
     default:
@@ -45,7 +47,8 @@ static void launch_lps(const Pipe& P, int slots, int lds, hipStream_t st, int ma
 }
 
 template <typename T>
-void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big, const Hooks& h) {
+void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big, const Hooks& h,
+                int part) {
   if (big && P.warena > 0 && pgs_lanes() == 16) {
     // the wide launch with LDS-resident B: one slot per wave (all four lane groups on it), a
     // small grid striding over the few slots past the main launch's rows
@@ -60,11 +63,11 @@ void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T 
   } else {
     if (blds) launch_lps<T, 16, true>(P, slots, lds, st, maxit, tol, scale, big, sp);
     else if (P.sqg && !big) launch_lps<T, 16, false, true>(P, slots, lds, st, maxit, tol, scale, big, sp);
-    else launch_lps<T, 16, false>(P, slots, lds, st, maxit, tol, scale, big, sp);
+    else launch_lps<T, 16, false>(P, slots, lds, st, maxit, tol, scale, big, sp, 0, part);  // the row-split launch
   }
 }
-template void launch_pgs<float>(const Pipe&, int, int, hipStream_t, int, float, float, int, const Hooks&);
-template void launch_pgs<double>(const Pipe&, int, int, hipStream_t, int, double, double, int, const Hooks&);
+template void launch_pgs<float>(const Pipe&, int, int, hipStream_t, int, float, float, int, const Hooks&, int);
+template void launch_pgs<double>(const Pipe&, int, int, hipStream_t, int, double, double, int, const Hooks&, int);
 
 // ---- S1 / S3 (the row builder and the finisher)
 template <typename T>
@@ -101,6 +104,24 @@ __global__ void __launch_bounds__(64) k_soccer_rows(DevModel<T> m, SoccerIds<T> 
   if (any_bad(e.qpos, m.nq)) { reset_env(m, e); warn++; }
   if (any_bad(e.qvel, m.nv)) { reset_env(m, e); warn++; }
   stage_rows(m, e, P, slot, warn);
+  if (P.qmh_pre) {
+    // Pipe.qmh_pre: the slots that end the step get euler()'s factorisation of qMH here, off the
+    // tail. The carry is written and the wave's LDS is dead: the factor is built in qLD's place.
+    const bool pre = P.qmh_pre == 2 || (e.nefc >> 2) >= P.split_blocks;
+    T* cr = P.at<T>(P.o_carry) + (size_t)slot * P.carry_stride;
+    int* cx = P.at<int>(P.o_carryi) + (size_t)slot * P.carryi_stride + m.L.carry_ints;
+    if (pre && m.has_damping) {
+      T* qg = cr + (m.L.qMH - m.L.qpos);
+      __threadfence();  // qMH was written to the carry by other lanes of this wave
+      wsync();
+      for (int k = lane_id(); k < m.nM; k += 64) e.qLD[k] = qg[k];
+      wsync();
+      const T di = factor_ld(m, e, e.qLD);
+      for (int k = lane_id(); k < m.nM; k += 64) qg[k] = e.qLD[k];
+      if (lane_id() < m.nv) cr[((m.L.carry_reals + 63) & ~63) + 256 + 8 + lane_id()] = di;
+    }
+    if (lane_id() == 0) cx[4] = pre && m.has_damping;
+  }
 }
 
 // The bank slots' settle steps (S3 of the extra slots), one wave per bank record, launched before
@@ -149,22 +170,47 @@ __global__ void __launch_bounds__(64) k_soccer_finish(DevModel<T> m, SoccerIds<T
                                                       const float* action, float* obs, double* reward,
                                                       uint8_t* terminated, uint8_t* truncated, float* final_obs,
                                                       int autoreset, uint64_t seed, int env_offset, int n_env,
-                                                      const uint8_t* mask, Pipe P, int banks) {
+                                                      const uint8_t* mask, Pipe P, int banks, int tier) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // tier (MGX_TAIL_FINISH; an env is heavy iff the row-split waves solved it, nefc / 4 >=
+  // split_blocks): 0 every env, as one launch. 1 the light envs, beside the heavy solver launch:
+  // the solver lists stay (that launch reads them) and an env that ended its episode is listed
+  // for tier 2 instead of reset, so the launch needs no ordering against the bank pipeline.
+  // 2 the heavy envs, resetting inline; the blocks past n_env install the listed resets.
   int env = blockIdx.x;
-  if (env >= n_env) return;
   int l = lane_id();
-  if (env == 0 && l == 0) {  // the solver lists are consumed; their sizes stay for diagnostics
+  Env<T> e;
+  if (tier == 2 && env >= n_env) {
+    env_bind(m, e, smem);
+    const int* dl = P.at<int>(P.o_defer);
+    const int cnt = dl[0];
+    for (int i = env - n_env; i < cnt; i += gridDim.x - n_env) {
+      const int de = dl[1 + i];
+      bool ok = banks && bank_install(m, e, ids, P, s, ev, obs, seed, env_offset, de);
+      if (l == 0) {
+        atomicAdd(P.ctr() + 9, 1);
+        if (!ok) P.at<int>(P.o_fix)[atomicAdd(P.ctr(), 1)] = de * 4 + FIX_RESET;
+      }
+      wsync();
+    }
+    return;
+  }
+  if (env >= n_env) return;
+  if (tier != 1 && env == 0 && l == 0) {  // the solver lists are consumed; their sizes stay for diagnostics
     P.ctr()[3] = P.ctr()[1];
     P.ctr()[4] = P.ctr()[2];
     P.ctr()[1] = 0;
     P.ctr()[2] = 0;
   }
-  if (env == 0)
+  if (tier != 1 && env == 0)
     for (int b = lane_id(); b < P.nbk; b += 64) P.at<int>(P.o_hist)[b] = 0;
-  Env<T> e;
   env_bind(m, e, smem);
   if (mask && !mask[env]) return;
+  if (tier) {
+    const bool heavy = (P.at<int>(P.o_ne)[env] >> 2) >= P.split_blocks;
+    if (heavy != (tier == 2)) return;
+    if (heavy && l == 0) atomicAdd(P.ctr() + 8, 1);
+  }
   int warn = load_carry(m, e, P, env);
   if (!finish_physics(m, e, P, env)) {
     load_template(m, e, P);
@@ -194,9 +240,17 @@ __global__ void __launch_bounds__(64) k_soccer_finish(DevModel<T> m, SoccerIds<T
   if (done && autoreset) {
     if (final_obs)
       for (int i = l; i < 80; i += 64) final_obs[(size_t)env * 80 + i] = o[i];
+    if (tier == 1) {
+      if (l == 0) {
+        int* dl = P.at<int>(P.o_defer);
+        dl[1 + atomicAdd(dl, 1)] = env;
+      }
+      return;
+    }
     __threadfence();
     wsync();
     bool ok = banks && bank_install(m, e, ids, P, s, ev, obs, seed, env_offset, env);
+    if (tier == 2 && l == 0) atomicAdd(P.ctr() + 10, 1);
     if (!ok && l == 0) {
       int i = atomicAdd(P.ctr(), 1);
       P.at<int>(P.o_fix)[i] = env * 4 + FIX_RESET;
@@ -223,19 +277,25 @@ template <typename T>
 void launch_soccer_finish(const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
                           const float* action, float* obs, double* reward, uint8_t* terminated, uint8_t* truncated,
                           float* final_obs, int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask,
-                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too) {
+                          const Pipe& P, int banks, int lds, hipStream_t st, bool bank_too, int tier) {
   if (bank_too && banks && P.R > 0) launch_soccer_bank_finish<T>(Mf, ids, n_env, P, 0, lds, st);
-  hipLaunchKernelGGL(k_soccer_finish<T>, dim3(n_env), dim3(64), lds, st, Mf, ids, s, ev, action, obs, reward, terminated,
-                     truncated, final_obs, autoreset, seed, env_offset, n_env, mask, P, banks);
+  // tier 2 (the heavy envs): a few more waves, which install the light envs' deferred resets
+  const int grid = n_env + (tier == 2 ? (n_env < MGX_TAIL_DEFER_GRID ? n_env : MGX_TAIL_DEFER_GRID) : 0);
+  hipLaunchKernelGGL(k_soccer_finish<T>, dim3(grid), dim3(64), lds, st, Mf, ids, s, ev, action, obs, reward, terminated,
+                     truncated, final_obs, autoreset, seed, env_offset, n_env, mask, P, banks, tier);
 }
 // the settle kernel takes the main solver launch's lanes per slot and register entries per lane
 // (launch_lps), so its PGS is the pipeline's
 template <typename T>
 void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const SoccerIds<T>& ids, const mgx_state& s,
                           const mgx_soccer_env& ev, const T* draws, float* obs, uint64_t seed, int env_offset, int n_env,
-                          const uint8_t* mask, const Pipe& P, int mode, int grid, int lds, hipStream_t st, int maxit, T tol,
-                          T scale) {
-#define MGX_SETTLE(E, L)                                                                                            \
+                          const uint8_t* mask, const Pipe& Pin, int mode, int grid, int lds, hipStream_t st, int maxit,
+                          T tol, T scale) {
+  // the settle builds its slots' rows itself (stage_rows), without the row builder's qMH factor:
+  // the slots' flags in the carry are the pipeline's and do not hold for it
+  Pipe P = Pin;
+  P.qmh_pre = 0;
+#define MGX_SETTLE(E, L)                                                                                       \
   hipLaunchKernelGGL((k_soccer_settle<T, E, L>), dim3(grid), dim3(64), lds, st, Ms, Mf, ids, s, ev, draws, obs, seed, \
                      env_offset, n_env, mask, P, mode, maxit, tol, scale)
   if (pgs_lanes() == 64) {
@@ -258,7 +318,7 @@ void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const So
   template void launch_soccer_finish<T>(const DevModel<T>&, const SoccerIds<T>&, const mgx_state&,                      \
                                         const mgx_soccer_env&, const float*, float*, double*, uint8_t*, uint8_t*, float*, \
                                         int, uint64_t, int, int, const uint8_t*, const Pipe&, int, int, hipStream_t,      \
-                                        bool);                                                                            \
+                                        bool, int);                                                                       \
   template void launch_soccer_settle<T>(const DevModel<T>&, const DevModel<T>&, const SoccerIds<T>&, const mgx_state&, \
                                         const mgx_soccer_env&, const T*, float*, uint64_t, int, int, const uint8_t*,    \
                                         const Pipe&, int, int, int, hipStream_t, int, T, T);

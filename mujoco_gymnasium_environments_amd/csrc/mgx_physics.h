@@ -37,6 +37,10 @@ struct Env {
   T qacc_ws, qfrc_applied, qfrc_smooth, qacc_smooth, qacc, qfrc_constraint, diaginv, time;
   int chainlen, madr;  // this lane's dof: chain length, dof_Madr
   uint64_t ancmask;
+  // qmh_done (wave-uniform): qMH already holds its factor and qmh_di its diaginv (the staged soccer
+  // row builder factorised it for a heavy slot; load_carry), so euler() skips factor_ld
+  int qmh_done;
+  T qmh_di;
 };
 
 // GB: B rows in global scratch (gB = this env's slice) instead of LDS (Layout.gB); EG: the per-row
@@ -80,6 +84,8 @@ __device__ __forceinline__ void env_bind(const DevModel<T>& m, Env<T>& e, char* 
   e.madr = l < m.nv ? m.dof_Madr[l] : 0;
   e.ancmask = l < m.nv ? m.dof_ancmask[l] : 0ull;
   e.overflow = 0;
+  e.qmh_done = 0;
+  e.qmh_di = 0;
 }
 
 // ---------------------------------------------------------------- state load / store / reset
@@ -1841,12 +1847,10 @@ __device__ __forceinline__ void rk4(const DevModel<T>& m, Env<T>& e) {
 template <typename T>
 __device__ __forceinline__ void euler(const DevModel<T>& m, Env<T>& e) {
   int l = lane_id();
-  bool damp = false;
-  for (int k = 0; k < m.nv; k++) damp |= m.dof_damping[k] > 0;
   T qa;
-  if (!damp) qa = e.qacc;
+  if (!m.has_damping) qa = e.qacc;
   else {
-    T di = factor_ld(m, e, e.qMH);
+    T di = e.qmh_done ? e.qmh_di : factor_ld(m, e, e.qMH);
     qa = solve_M(m, e, e.qMH, di, e.qfrc_smooth + e.qfrc_constraint);
   }
   if (l < m.nv) e.qvel[l] += m.timestep * qa;

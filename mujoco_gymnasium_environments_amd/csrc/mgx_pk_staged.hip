@@ -406,7 +406,7 @@ int step_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms,
     hipLaunchKernelGGL(k_pk_rows<T>, dim3(slots), dim3(64), m->Ls.bytes, st, Ms, ids, *s, action, e->action_f64, n_env,
                        mask, P, banks, k);
     MGX_PK_EPL(pk_epl(M), hipLaunchKernelGGL((k_pgs_groups<T, E, PK_LPS, false>), dim3(grid), dim3(64), mlds, st, P,
-                                             M.iterations, M.tolerance, scale, spw, 0));
+                                             M.iterations, M.tolerance, scale, spw, 0, 0));
     if (banks && P.R > 0)
       hipLaunchKernelGGL(k_pk_bank_finish<T>, dim3(n_env * P.R), dim3(64), m->Lf.bytes, st, Mf, ids, n_env, P);
     hipLaunchKernelGGL(k_pk_finish<T>, dim3(n_env), dim3(64), m->Lf.bytes, st, Mf, ids, *s, *e, action, obs, reward,

@@ -586,7 +586,7 @@ void launch_rk_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit,
   const int spw = 64 / RK_LPS;
   const int grid = (slots + spw - 1) / spw;
   hipLaunchKernelGGL((k_pgs_groups<T, RK_EPL, RK_LPS, false, true, true>), dim3(grid), dim3(64), lds, st, P, maxit, tol, scale,
-                     spw, big);
+                     spw, big, 0);
 }
 
 template <typename T>

@@ -48,7 +48,10 @@ __host__ __device__ constexpr int mgx_twl(bool dofb) { return dofb ? 4 : 8; }  /
 #define MGX_PGS_LDS_ROWS 192   // rows per slot the main solver launch keeps in LDS (2 waves / CU in fp64)
 #define MGX_PGS_SPLIT_BLOCKS 40  // soccer main launch: slots of at least this many blocks are solved row-split, one per wave
 #define MGX_BANK_STREAM 1      // soccer: the reset banks' pipeline on its own stream (0: off; 1 / 2: soccer_step_staged)
-#define MGX_PGS_WIDE_GRID 256 // waves of the global-B launch (slots over MGX_PGS_LDS_ROWS, waves over their arena)
+#define MGX_TAIL_FINISH 1      // soccer: heavy solver waves on a side stream, light envs finished beside them (0: off)
+#define MGX_TAIL_HEAVY_GRID 1024  // waves of the heavy solver launch (grid-stride over the row-split slots)
+#define MGX_TAIL_DEFER_GRID 256   // waves of the tail finisher that install the light envs' deferred resets
+#define MGX_PGS_WIDE_GRID 256// waves of the global-B launch (slots over MGX_PGS_LDS_ROWS, waves over their arena)
 #define MGX_PGS_WIDE_LDS_GRID 32  // waves of the wide launch with LDS-resident B (one slot per wave)
 #define MGX_PGS_ARENA_F64 49152  // LDS arena per main-launch solver wave of 4 slots, fp64 (tools/pgs_census.py)
 #define MGX_PGS_ARENA_F32 32768  //                                                    fp32
@@ -108,11 +111,25 @@ struct Pipe {
   // is still to be finished (the row builder sets it, a restart of the record clears it): the bank
   // finisher advances exactly the records whose rows were built, wherever it sits in the step.
   size_t o_ctr2, o_hist2, o_blist2, o_k2list2, o_k2big2, o_bstg;
+  // The tail finisher's deferred resets (MGX_TAIL_FINISH): [0] their count, [1 + i] the i-th env.
+  // The light envs' finisher lists an env that ended its episode here instead of resetting it; the
+  // heavy envs' finisher, ordered behind the bank pipeline, installs them. The bulk solver launch
+  // clears the count.
+  size_t o_defer;
+  // Soccer, with the tail finisher: the row builder factorises qMH = M + h damping for the slots
+  // whose finish ends the step (1: the heavy slots; 2: every slot, the MGX_TAIL_FACTOR test hook;
+  // 0: none), which euler() would otherwise do in the finisher: the factor replaces qMH in the
+  // carry, its diaginv goes to the carry's fifth register row (from real 8; real 0 is the time)
+  // and spare int 4 flags it. Same function on the same inputs: the same bits.
+  int qmh_pre;
   template <typename X> __device__ __forceinline__ X* at(size_t off) const { return reinterpret_cast<X*>(base + off); }
   // [0] fixup count, [1] solver-list count, [2] wide-solver-list count, [3] / [4] the last
   // step's list sizes, [5] RK4 step: fixup count (k_pgs_groups clears [0] at every launch),
   // [6] / [7] since the workspace was initialised: slots over capE rows solved in split mode /
-  // listed by the row builder (equal when split_blocks > 0; tests/test_gpu_pgs_split.py)
+  // listed by the row builder (equal when split_blocks > 0; tests/test_gpu_pgs_split.py),
+  // [8] / [9] / [10] since then, with MGX_TAIL_FINISH: env-steps finished by the heavy envs'
+  // finisher / resets it took from the deferred list / resets of its own envs
+  // (tests/test_gpu_tail_finish.py)
   __device__ __forceinline__ int* ctr() const { return at<int>(o_ctr); }
 };
 
@@ -1107,11 +1124,17 @@ __device__ __forceinline__ int split_count(const Pipe& P) {
 }
 
 template <typename T, int EPL, int LPS, bool BLDS, bool SQG = false, bool DOFB = false>
-__global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T scale, int spw, int big) {
+__global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T scale, int spw, int big, int part) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // part (main launch, MGX_TAIL_FINISH): 0 every virtual wave; 1 only the K row-split waves (the
+  // heavy launch, on a side stream); 2 only the others (the bulk launch, on the caller's stream)
   // fixup list count, filled by the finisher (the live view's; on the bank view this word of its
-  // own counter block is unused)
-  if (!big && blockIdx.x == 0 && threadIdx.x == 0) P.ctr()[0] = 0;
+  // own counter block is unused); of the two parts the bulk launch clears it, and the deferred
+  // resets' count with it
+  if (!big && part != 1 && blockIdx.x == 0 && threadIdx.x == 0) {
+    P.ctr()[0] = 0;
+    if (part == 2) P.at<int>(P.o_defer)[0] = 0;
+  }
   const int cnt = P.ctr()[big ? 2 : 1];
   const int* list = P.at<int>(P.o_k2big);
   const int spn = spw < 0 ? -spw : spw;
@@ -1128,7 +1151,8 @@ __global__ void __launch_bounds__(64) k_pgs_groups(Pipe P, int maxit, T tol, T s
     if (!big && P.split_blocks > 0) K = min(split_count(P), cnt);
   }
   const int nw = K + (cnt - K + spn - 1) / spn;
-  for (int w = blockIdx.x; w < nw; w += gridDim.x) {
+  const int w0 = part == 2 ? K : 0, w1 = part == 1 ? K : nw;
+  for (int w = w0 + blockIdx.x; w < w1; w += gridDim.x) {
     if constexpr (CAN_SPLIT) {
       if (w < K) {
         const int slot = __builtin_amdgcn_readfirstlane(sorted_slot(P, w, LPS));
@@ -1188,6 +1212,9 @@ __device__ __forceinline__ int load_carry(const DevModel<T>& m, Env<T>& e, const
   e.time = rg[256];
   const int* ci = P.at<int>(P.o_carryi) + (size_t)slot * P.carryi_stride;
   const int* cx = ci + m.L.carry_ints;
+  // the row builder's qMH factor (Pipe.qmh_pre; the settle's pipe never has it)
+  e.qmh_done = P.qmh_pre ? cx[4] : 0;
+  e.qmh_di = e.qmh_done && l < m.nv ? rg[256 + 8 + l] : (T)0;
   e.ncon = cx[0];
   e.nefc = cx[1];
   e.overflow = cx[2];

@@ -928,6 +928,71 @@ int64_t mgx_transition_fd_bytes(const mgx_model *m, int slots);
 int mgx_transition_fd(const mgx_model *m, const mgx_state *state, const mgx_fd_io *io, int n_env,
                       const uint8_t *env_mask, void *stream);
 
+/* ---- open-loop rollouts (MuJoCo's mujoco.rollout [ext]) --------------------------------------- */
+/* From each env's state, n_roll = K rollouts of n_step = T recorded steps under given control
+ * sequences; each recorded step is nsub >= 1 mgx_step substeps with ctrl held (mgx_fd_io.nsub).
+ * The state vector is mjSTATE_FULLPHYSICS without activations (the models have none):
+ * [time, qpos[nq], qvel[nv]], nstate = 1 + nq + nv, in the model's real type. Rollout k of env e is
+ * virtual env v = e K + k; every array below is indexed [N][K]... = [v]... .
+ * Inputs (device memory, each nullable):
+ *   initial_state      [N][K][nstate]; NULL: every rollout starts from its env's current time, qpos, qvel
+ *   initial_warmstart  [N][K][nv];     NULL: the env's own qacc_warmstart
+ *   ctrl               [N][K][ceil(T / hold)][nu]: knot j is applied during recorded steps
+ *                      j hold .. j hold + hold - 1 (zero-order hold, hold >= 1). With
+ *                      MGX_ROLLOUT_SHARED_CTRL it is [K][ceil(T / hold)][nu], shared by all envs.
+ *                      NULL: the env's current ctrl is held for the whole rollout. Values are used
+ *                      as given: clamping to actuator_ctrlrange is the step's job, as in mgx_step.
+ *   qfrc_applied and xfrc_applied are the env's own, held constant.
+ * Outputs (device memory, each nullable):
+ *   state       [N][K][T][nstate]: row t is the state after recorded step t
+ *   sensordata  [N][K][T][nsensordata]: row t is mgx_forward + mgx_sensor evaluated at state[t] with
+ *               the step's ctrl still applied: the values of the CURRENT state, which is what
+ *               mgx_sensor gives after an mgx_step. This deliberately differs from MuJoCo, whose
+ *               data.sensordata after mj_step belongs to the last substep's pre-integration state.
+ *               Needs mgx_sensor_configure; a model that mgx_forward refuses (more than 64 dofs,
+ *               elliptic cones) returns that same MGX_E_UNSUPPORTED before anything is launched; a
+ *               model without sensors writes nothing for this output.
+ *   n_done      int32 [N][K]: recorded steps completed before the rollout diverged, T if it did not
+ * Divergence follows MuJoCo's rollout: stop and pad. A rollout has diverged at recorded step t if
+ * that step raised the virtual env's `warning` count (the bad-state auto-reset of mj_checkPos /
+ * mj_checkVel / mj_checkAcc). Then n_done = t, rows t .. T-1 of state (and of sensordata) all hold
+ * what that step left behind, after its reset, and the rollout takes no part in any later mgx_step /
+ * mgx_forward / mgx_sensor launch of the call.
+ * Nothing in the caller's mgx_state is written. Rows of envs that env_mask deselects are left
+ * untouched and every byte of a selected env's non-NULL outputs is written. The call is asynchronous
+ * on the one stream, neither allocates nor synchronises (graph-capturable), and its host loop over
+ * passes and steps issues launches only. No atomics: results are bit-reproducible.
+ * Not provided: actuator activations, mocap / userdata state, per-step control of the applied
+ * forces, and rollouts through a task's fused env step (mgx_soccer_step ...). */
+#define MGX_ROLLOUT_SHARED_CTRL 1
+
+typedef struct mgx_rollout_io {
+  int32_t n_roll, n_step;          /* K, T: both >= 1 */
+  int32_t nsub, hold;              /* mj_steps per recorded step; recorded steps per ctrl knot: both >= 1 */
+  int32_t flags, slots;            /* MGX_ROLLOUT_* bits; virtual envs the workspace holds, >= 1 */
+  const void *initial_state;       /* [N][K][nstate], nullable */
+  const void *initial_warmstart;   /* [N][K][nv], nullable */
+  const void *ctrl;                /* [N][K][ceil(T/hold)][nu] ([K][..][nu] when shared), nullable */
+  void *state;                     /* [N][K][T][nstate], nullable */
+  void *sensordata;                /* [N][K][T][nsensordata], nullable */
+  int32_t *n_done;                 /* [N][K], nullable */
+  void *workspace;                 /* device memory, mgx_rollout_bytes(m, slots, sensordata != NULL) bytes */
+  uint64_t workspace_bytes;
+} mgx_rollout_io;
+
+/* The workspace holds `slots` virtual envs, each a complete mgx_state plus scratch_bytes_per_env of
+ * solver scratch where the model needs it and a live flag; with_sensors != 0 adds per slot the
+ * buffers of an mgx_forward_out and one sensordata staging row (0 reals before
+ * mgx_sensor_configure). Its contents need no initialisation. Passes run over ranges of v, not of
+ * envs: any slots >= 1 is legal and the last pass may be partial. */
+int64_t mgx_rollout_bytes(const mgx_model *m, int slots, int with_sensors);
+
+/* MGX_E_ARG for n_roll, n_step, nsub, hold or slots below 1, unknown flag bits, a NULL state or io,
+ * or a workspace smaller than mgx_rollout_bytes. With no output requested the call returns MGX_OK
+ * and launches nothing. */
+int mgx_rollout(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io, int n_env,
+                const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .native import MGX_F32, MGX_F64, check, lib
 from .dynamics import DynamicsMethods
 from .rays import RayMethods
 from .sensors import SensorMethods
+from .rollouts import RolloutMethods
 from .transitions import TransitionMethods
 
 DEBUG_FIELDS = ["xpos", "xquat", "xipos", "subtree_com", "cinert", "cdof", "qM", "qLD", "geom_xpos", "geom_xmat",
@@ -60,7 +61,7 @@ class NativeModel:
             self.handle = None
 
 
-class PhysicsBatch(RayMethods, SensorMethods, DynamicsMethods, TransitionMethods):
+class PhysicsBatch(RayMethods, SensorMethods, DynamicsMethods, TransitionMethods, RolloutMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

@@ -314,6 +314,17 @@ class MgxFdIO(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("slots", C.c_int32), ("pad0", C.c_int32)]
 
 
+MGX_ROLLOUT_SHARED_CTRL = 1  # include/mgx.h mgx_rollout_io.flags
+
+
+class MgxRolloutIO(C.Structure):
+    _fields_ = [("n_roll", C.c_int32), ("n_step", C.c_int32), ("nsub", C.c_int32), ("hold", C.c_int32),
+                ("flags", C.c_int32), ("slots", C.c_int32), ("initial_state", C.c_void_p),
+                ("initial_warmstart", C.c_void_p), ("ctrl", C.c_void_p), ("state", C.c_void_p),
+                ("sensordata", C.c_void_p), ("n_done", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64)]
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

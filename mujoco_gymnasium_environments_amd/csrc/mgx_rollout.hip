@@ -1,0 +1,214 @@
+// mgx_rollout.hip — open-loop rollouts (MuJoCo's mujoco.rollout [ext]) and their C-ABI:
+// mgx_rollout_bytes, mgx_rollout (include/mgx.h).
+//
+// Rollout k of env e is virtual env v = e K + k. A pass materialises a range of v in the caller's
+// workspace (the virtual-env workspace of mgx_transition_fd held for T steps instead of one) and
+// steps it with mgx_step itself, so a rollout is bit for bit the step() the user runs:
+//   k_rollout_begin   one wave per virtual env: copies the env's state rows, or an initial_state /
+//                     initial_warmstart row, the applied forces and the step-0 ctrl (coalesced),
+//                     zeroes warning / overflow and writes the live flag;
+//   per recorded step t:
+//     mgx_step        on the workspace's mgx_state, nsub substeps, no frames, masked by the live flags;
+//     mgx_forward + mgx_sensor   (sensordata requested) at the new state into the staging rows;
+//     k_rollout_record  one wave per virtual env: the state row, the sensordata row, the next
+//                     step's ctrl; on divergence n_done, the padding rows and the live flag.
+// No atomics anywhere: results are bit-reproducible.
+#include "mgx_internal.h"
+#include "mgx_rollout.h"
+#include "mgx_sensor.h"
+
+using namespace mgx;
+
+namespace {
+
+// ------------------------------------------------------------------ begin
+// Block b of the pass is virtual env v = v0 + b in slot b.
+template <typename T>
+__global__ void __launch_bounds__(64) k_rollout_begin(mgx_state s, RolloutBuf<T> w, int v0, const uint8_t* mask) {
+  const int b = blockIdx.x, l = threadIdx.x;
+  const int v = v0 + b, env = v / w.K, k = v - env * w.K;
+  const bool on = !mask || mask[env] != 0;  // one byte, the same for every lane
+  if (l == 0) w.live[b] = on ? 1 : 0;
+  if (!on) return;
+  const int nq = w.nq, nv = w.nv, nu = w.nu, nx = w.nx;
+  const size_t nstate = (size_t)1 + nq + nv;
+  const T* row = w.in_state ? w.in_state + (size_t)v * nstate : nullptr;
+  const T* sq = row ? row + 1 : (const T*)s.qpos + (size_t)env * nq;
+  const T* sv = row ? row + 1 + nq : (const T*)s.qvel + (size_t)env * nv;
+  const T* sa = w.in_warm ? w.in_warm + (size_t)v * nv : (const T*)s.qacc_warmstart + (size_t)env * nv;
+  const T* sf = (const T*)s.qfrc_applied + (size_t)env * nv;
+  const T* sx = (const T*)s.xfrc_applied + (size_t)env * nx;
+  // knot 0 of the rollout's schedule, or the env's ctrl held throughout
+  const T* sc = w.in_ctrl ? w.in_ctrl + (size_t)(w.shared ? k : v) * w.nknot * nu : (const T*)s.ctrl + (size_t)env * nu;
+  for (int i = l; i < nq; i += 64) w.qpos[(size_t)b * nq + i] = sq[i];
+  for (int i = l; i < nv; i += 64) {
+    w.qvel[(size_t)b * nv + i] = sv[i];
+    w.qacc[(size_t)b * nv + i] = sa[i];
+    w.qfrc[(size_t)b * nv + i] = sf[i];
+  }
+  for (int i = l; i < nu; i += 64) w.ctrl[(size_t)b * nu + i] = sc[i];
+  for (int i = l; i < nx; i += 64) w.xfrc[(size_t)b * nx + i] = sx[i];
+  if (l == 0) {
+    w.time[b] = row ? row[0] : ((const T*)s.time)[env];
+    w.warning[b] = 0;
+    w.overflow[b] = 0;
+  }
+}
+
+// ------------------------------------------------------------------ record
+// After recorded step t. The live flag and the warning count are loaded by one lane and broadcast,
+// so `live` and `diverged` are scalars and the branches on them are uniform. A rollout that is
+// not live (deselected env, or diverged at an earlier step) has every output row already.
+template <typename T>
+__global__ void __launch_bounds__(64) k_rollout_record(RolloutBuf<T> w, int v0, int t) {
+  const int b = blockIdx.x, l = threadIdx.x;
+  int flags = 0;
+  if (l == 0) flags = (w.live[b] ? 1 : 0) | (w.warning[b] != 0 ? 2 : 0);
+  flags = __builtin_amdgcn_readfirstlane(flags);
+  if (!(flags & 1)) return;
+  const bool diverged = (flags & 2) != 0;
+  const int v = v0 + b, nq = w.nq, nv = w.nv, nu = w.nu, nsd = w.nsd, Tn = w.T_steps;
+  const int nstate = 1 + nq + nv;
+  // rows t .. t_end - 1 take what this step left: one row, or the padding to the end
+  const int t_end = diverged ? Tn : t + 1;
+  if (w.out_state) {
+    const T* q = w.qpos + (size_t)b * nq;
+    const T* qv = w.qvel + (size_t)b * nv;
+    const T tm = w.time[b];
+    for (int i = l; i < nstate; i += 64) {
+      const T x = i == 0 ? tm : (i <= nq ? q[i - 1] : qv[i - 1 - nq]);
+      for (int r = t; r < t_end; r++) w.out_state[((size_t)v * Tn + r) * nstate + i] = x;
+    }
+  }
+  if (w.out_sens && w.sens) {
+    const T* sd = w.sens + (size_t)b * nsd;
+    for (int i = l; i < nsd; i += 64) {
+      const T x = sd[i];
+      for (int r = t; r < t_end; r++) w.out_sens[((size_t)v * Tn + r) * nsd + i] = x;
+    }
+  }
+  if (diverged) {
+    if (l == 0) {
+      if (w.n_done) w.n_done[v] = t;
+      w.live[b] = 0;
+    }
+    return;
+  }
+  if (t + 1 == Tn) {
+    if (l == 0 && w.n_done) w.n_done[v] = Tn;
+    return;
+  }
+  // zero-order hold: the next step changes ctrl only where a new knot begins
+  if (w.in_ctrl && (t + 1) % w.hold == 0) {
+    const int K = w.K, k = v % K;
+    const T* sc = w.in_ctrl + ((size_t)(w.shared ? k : v) * w.nknot + (t + 1) / w.hold) * nu;
+    for (int i = l; i < nu; i += 64) w.ctrl[(size_t)b * nu + i] = sc[i];
+  }
+}
+
+int rollout_dims(const mgx_model* m, RolloutDims* d) {
+  mgx_model_info info;
+  const int rc = mgx_model_get_info(m, &info);
+  if (rc) return rc;
+  *d = RolloutDims{info.nq, info.nv, info.nu, info.nbody, m->precision == MGX_F32 ? 4 : 8, info.max_ncon,
+                   m->sensor && !m->sensor->unsupported ? m->sensor->nsensordata : 0,
+                   (size_t)info.scratch_bytes_per_env};
+  return MGX_OK;
+}
+
+template <typename T>
+int run_rollout(const mgx_model* m, const RolloutDims& d, const mgx_state* s, const mgx_rollout_io* io, bool sensors,
+                int n_env, const uint8_t* mask, hipStream_t st) {
+  const RolloutLayout o = rollout_layout(d, io->slots, sensors);
+  char* ws = (char*)io->workspace;
+  const int Tn = io->n_step, K = io->n_roll;
+  RolloutBuf<T> w{};
+  w.qpos = (T*)(ws + o.qpos); w.qvel = (T*)(ws + o.qvel); w.qacc = (T*)(ws + o.qacc); w.ctrl = (T*)(ws + o.ctrl);
+  w.qfrc = (T*)(ws + o.qfrc); w.xfrc = (T*)(ws + o.xfrc); w.time = (T*)(ws + o.time);
+  w.warning = (int32_t*)(ws + o.warning); w.overflow = (int32_t*)(ws + o.overflow); w.live = (uint8_t*)(ws + o.live);
+  w.sens = sensors ? (const T*)(ws + o.sens) : nullptr;
+  w.in_state = (const T*)io->initial_state; w.in_warm = (const T*)io->initial_warmstart; w.in_ctrl = (const T*)io->ctrl;
+  w.out_state = (T*)io->state; w.out_sens = sensors ? (T*)io->sensordata : nullptr; w.n_done = io->n_done;
+  w.nq = d.nq; w.nv = d.nv; w.nu = d.nu; w.nx = 6 * d.nbody; w.nsd = d.nsd;
+  w.K = K; w.T_steps = Tn; w.hold = io->hold; w.nknot = (Tn + io->hold - 1) / io->hold;
+  w.shared = io->flags & MGX_ROLLOUT_SHARED_CTRL ? 1 : 0;
+  mgx_state vs{};
+  vs.qpos = w.qpos; vs.qvel = w.qvel; vs.qacc_warmstart = w.qacc; vs.ctrl = w.ctrl; vs.qfrc_applied = w.qfrc;
+  vs.xfrc_applied = w.xfrc; vs.time = w.time; vs.warning = w.warning; vs.overflow = w.overflow;
+  vs.scratch = d.scratch ? ws + o.scratch : nullptr;
+  mgx_forward_out fo{};
+  if (sensors) {
+    fo.qacc = ws + o.f_qacc; fo.qfrc_constraint = ws + o.f_qfrc; fo.ncon = (int32_t*)(ws + o.f_ncon);
+    fo.con_geom = (int32_t*)(ws + o.f_geom); fo.con_dist = ws + o.f_dist; fo.con_pos = ws + o.f_pos;
+    fo.con_frame = ws + o.f_frame; fo.con_force = ws + o.f_force;
+  }
+  const bool need_fwd = sensors && m->sensor->need_acc;
+  const int64_t total = (int64_t)n_env * K;
+  for (int64_t v0 = 0; v0 < total; v0 += io->slots) {
+    const int cnt = (int)(total - v0 < io->slots ? total - v0 : io->slots);
+    hipLaunchKernelGGL(k_rollout_begin<T>, dim3(cnt), dim3(64), 0, st, *s, w, (int)v0, mask);
+    MGX_HIPCHK(hipGetLastError());
+    for (int t = 0; t < Tn; t++) {
+      // the library's own step, exactly as a caller of mgx_step gets it; rollouts of deselected
+      // envs hold no state, and diverged ones are done: both are masked out by the live flags
+      int rc = mgx_step(m, &vs, nullptr, cnt, io->nsub, w.live, st);
+      if (rc) return rc;
+      if (sensors) {
+        if (need_fwd) {
+          rc = mgx_forward(m, &vs, &fo, cnt, w.live, st);
+          if (rc) return rc;
+        }
+        rc = mgx_sensor(m, &vs, need_fwd ? &fo : nullptr, ws + o.sens, cnt, w.live, st);
+        if (rc) return rc;
+      }
+      hipLaunchKernelGGL(k_rollout_record<T>, dim3(cnt), dim3(64), 0, st, w, (int)v0, t);
+      MGX_HIPCHK(hipGetLastError());
+    }
+  }
+  return MGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mgx_rollout_bytes(const mgx_model* m, int slots, int with_sensors) {
+  if (!m || slots < 1) return host_fail(MGX_E_ARG, "null model or slots < 1");
+  RolloutDims d;
+  const int rc = rollout_dims(m, &d);
+  if (rc) return rc;
+  return (int64_t)rollout_layout(d, slots, with_sensors != 0).bytes;
+}
+
+int mgx_rollout(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, int n_env, const uint8_t* env_mask,
+                void* stream) {
+  if (!m || !io || n_env < 0) return host_fail(MGX_E_ARG, "null argument or n_env < 0");
+  int rc = host_check_state(s);
+  if (rc) return rc;
+  if (io->flags & ~MGX_ROLLOUT_SHARED_CTRL) return host_fail(MGX_E_ARG, "unknown mgx_rollout_io.flags bits");
+  if (io->n_roll < 1 || io->n_step < 1) return host_fail(MGX_E_ARG, "n_roll and n_step must be >= 1");
+  if (io->nsub < 1 || io->hold < 1) return host_fail(MGX_E_ARG, "nsub and hold must be >= 1");
+  if (io->slots < 1) return host_fail(MGX_E_ARG, "slots must be >= 1");
+  if ((int64_t)n_env * io->n_roll > INT32_MAX) return host_fail(MGX_E_ARG, "n_env * n_roll exceeds 2^31 - 1");
+  bool sensors = false;
+  if (io->sensordata) {
+    // what mgx_forward and mgx_sensor would refuse, before anything is launched
+    if (m->wide) return host_fail(MGX_E_UNSUPPORTED, std::string("mgx_forward: ") + MGX_WIDE_MSG);
+    if ((m->precision == MGX_F32 ? m->mf.cone : m->md.cone) != 0)
+      return host_fail(MGX_E_UNSUPPORTED, "mgx_forward decodes pyramidal cones only");
+    if (!m->sensor) return host_fail(MGX_E_ARG, "mgx_sensor_configure has not been called for this model");
+    if (m->sensor->unsupported) return host_fail(MGX_E_UNSUPPORTED, m->sensor->why);
+    sensors = m->sensor->nsensordata > 0;
+  }
+  RolloutDims d;
+  rc = rollout_dims(m, &d);
+  if (rc) return rc;
+  if (!io->workspace || io->workspace_bytes < rollout_layout(d, io->slots, io->sensordata != nullptr).bytes)
+    return host_fail(MGX_E_ARG, "workspace smaller than mgx_rollout_bytes");
+  if (n_env == 0 || (!io->state && !sensors && !io->n_done)) return MGX_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (m->precision == MGX_F32) return run_rollout<float>(m, d, s, io, sensors, n_env, env_mask, st);
+  return run_rollout<double>(m, d, s, io, sensors, n_env, env_mask, st);
+}
+
+}  // extern "C"

@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..dynamics import DynamicsForwarding
+from ..rollouts import RolloutForwarding
 from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
@@ -111,7 +112,7 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
+class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

@@ -30,6 +30,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..dynamics import DynamicsForwarding
+from ..rollouts import RolloutForwarding
 from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
@@ -86,7 +87,7 @@ class ConstructionTables:
         return np.array([task, rng.uniform(0, 5), rng.uniform(0, 0.5), rng.uniform(15, 35)], dtype=np.float64)
 
 
-class ConstructionVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
+class ConstructionVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` humanoid_construction envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 50}

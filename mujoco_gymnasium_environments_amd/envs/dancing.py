@@ -31,6 +31,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..dynamics import DynamicsForwarding
+from ..rollouts import RolloutForwarding
 from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
@@ -115,7 +116,7 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
+class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

@@ -24,6 +24,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import check, lib
 from ..dynamics import DynamicsForwarding
+from ..rollouts import RolloutForwarding
 from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
@@ -101,7 +102,7 @@ class MartialTables:
         return np.array([rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5)])
 
 
-class MartialArtsVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
+class MartialArtsVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` humanoid_martial_arts envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 60}

@@ -24,6 +24,7 @@ from .. import cabi, mjcf
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..native import NativeError, check, lib
 from ..dynamics import DynamicsForwarding
+from ..rollouts import RolloutForwarding
 from ..transitions import TransitionForwarding
 from ..rays import RayForwarding
 from ..sensors import SensorForwarding
@@ -116,7 +117,7 @@ class ParkourTables:
         return np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.0, 1.0)])
 
 
-class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding):
+class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` quadruped_parkour envs stepping in lockstep on one GPU."""
 
     metadata = {'render_modes': [], 'render_fps': 100}

@@ -236,6 +236,44 @@ class StreamShardedEnv:
                                          out=full.rows(a, b), **kw)
         return TransitionResult(**{f: getattr(full, f) for f in FD_OUTPUTS if getattr(part, f) is not None})
 
+    @property
+    def state_size(self) -> int:
+        return self.shards[0].batch.state_size
+
+    def get_state(self) -> torch.Tensor:
+        return torch.cat([s.batch.get_state() for s in self.shards])
+
+    def set_state(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
+        for (a, b), s in zip(self.bounds, self.shards):
+            s.batch.set_state(x[a:b], mask=None if mask is None else mask[a:b])
+
+    def physics_rollout(self, ctrl=None, nstep=None, initial_state=None, initial_warmstart=None, hold: int = 1,
+                        shared_ctrl: bool = False, sensordata: bool = False, mask: Optional[torch.Tensor] = None,
+                        stream=None, only=None, **kw):
+        """PhysicsBatch.rollout over every shard, into slices of one set of tensors (allocated once
+        per (K, T, sensordata)); launched on the caller's stream. The name and the meaning of
+        ``ctrl`` are those of RolloutForwarding.physics_rollout (``rollout`` is the episode sums)."""
+        from ..rollouts import ROLLOUT_OUTPUTS, RolloutResult, alloc_rollout, rollout_shape
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        b0, m = self.shards[0].batch, self.model
+        k, t = rollout_shape(self.num_envs, int(m.nu), ctrl, nstep, initial_state, initial_warmstart, hold, shared_ctrl)
+        sensordata = sensordata if only is None else "sensordata" in only
+        cache = self.__dict__.setdefault("_rollout_out", {})
+        key = (k, t, bool(sensordata))
+        if key not in cache:
+            if t < 1:
+                return b0.rollout(nstep=t, hold=hold, **kw)  # the library refuses it and names the argument
+            cache[key] = alloc_rollout(self.num_envs, k, t, b0.state_size, int(m.nsensordata), b0.dtype, self.device,
+                                       sensordata)
+        full, part = cache[key], None
+        cut = lambda x, a, b: None if x is None else x[a:b]  # noqa: E731
+        for (a, b), s in zip(self.bounds, self.shards):
+            part = s.batch.rollout(ctrl=ctrl if shared_ctrl else cut(ctrl, a, b), nstep=t,
+                                   initial_state=cut(initial_state, a, b), initial_warmstart=cut(initial_warmstart, a, b),
+                                   hold=hold, shared_ctrl=shared_ctrl, sensordata=sensordata, mask=cut(mask, a, b),
+                                   stream=cs, only=only, out=full.rows(a, b), **kw)
+        return RolloutResult(**{f: getattr(full, f) for f in ROLLOUT_OUTPUTS if getattr(part, f) is not None})
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

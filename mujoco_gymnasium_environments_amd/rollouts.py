@@ -1,0 +1,209 @@
+"""Batched open-loop rollouts on the device (mgx_rollout, include/mgx.h): MuJoCo's
+``mujoco.rollout``.
+
+``RolloutMethods`` gives :class:`~.batch.PhysicsBatch` its ``rollout`` / ``get_state`` /
+``set_state``; ``RolloutForwarding`` gives the ``*VectorEnv`` classes the same call, forwarded to
+their batch.
+
+From every env's state (or from given initial states), K rollouts of T recorded steps under K
+control sequences: ``state`` [N, K, T, nstate] with the state vector ``[time, qpos, qvel]``
+(mjSTATE_FULLPHYSICS; the models have no activations), optionally ``sensordata`` [N, K, T,
+nsensordata], and ``n_done`` [N, K]. The call steps virtual copies of the envs in a workspace of
+its own with the library's own step, so a rollout is bit for bit what ``step()`` would do; it writes
+nothing to the batch's state.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import torch
+
+from . import cabi
+from .native import check, lib
+from .sensors import _ptr, _stream
+
+ROLLOUT_OUTPUTS = ("state", "sensordata", "n_done")
+WORKSPACE_LIMIT = 1 << 30  # slots=None keeps the workspace under this many bytes (one virtual env at least)
+
+
+class RolloutResult:
+    """state [N, K, T, nstate] (row t: ``[time, qpos, qvel]`` after recorded step t), sensordata
+    [N, K, T, nsensordata] (the sensors at that state, as ``sensordata()`` gives them after a
+    ``step()``) and n_done int32 [N, K]: the recorded steps completed before the rollout diverged
+    (a bad-state auto-reset), T if it did not; rows n_done .. T-1 repeat what the diverging step
+    left behind. A field the call did not request is None. Tensors the call allocated are owned by
+    the batch and overwritten by the next call of the same shape."""
+
+    __slots__ = ROLLOUT_OUTPUTS
+
+    def __init__(self, **fields):
+        for f in ROLLOUT_OUTPUTS:
+            setattr(self, f, fields.get(f))
+
+    def rows(self, a: int, b: int) -> "RolloutResult":
+        return RolloutResult(**{f: None if getattr(self, f) is None else getattr(self, f)[a:b] for f in ROLLOUT_OUTPUTS})
+
+
+def alloc_rollout(n, k, t, nstate, nsensordata, dtype, device, sensordata=True) -> RolloutResult:
+    z = lambda *shape: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+    return RolloutResult(state=z(n, k, t, nstate), sensordata=z(n, k, t, nsensordata) if sensordata else None,
+                         n_done=torch.zeros(n, k, dtype=torch.int32, device=device))
+
+
+def rollout_shape(n, nu, ctrl, nstep, initial_state, initial_warmstart, hold, shared_ctrl):
+    """(K, T) of a rollout call, inferred from ``ctrl`` / ``initial_state`` / ``initial_warmstart``.
+    ``ctrl`` is [N, K, ceil(T / hold), nu] ([K, ceil(T / hold), nu] when shared): without ``nstep``,
+    T is its knots times ``hold``."""
+    k = None
+    lead = 0 if shared_ctrl else 1
+    if ctrl is not None:
+        if ctrl.dim() != 3 + lead or ctrl.shape[-1] != nu or (lead and ctrl.shape[0] != n):
+            raise ValueError(f"ctrl must be {'[K' if shared_ctrl else '[N, K'}, ceil(T / hold), nu], got {tuple(ctrl.shape)}")
+        k = int(ctrl.shape[lead])
+        if nstep is None:
+            nstep = int(ctrl.shape[lead + 1]) * int(hold)
+    for name, t in (("initial_state", initial_state), ("initial_warmstart", initial_warmstart)):
+        if t is None:
+            continue
+        if t.dim() != 3 or t.shape[0] != n or (k is not None and t.shape[1] != k):
+            raise ValueError(f"{name} must be [N, K, width] with the K of the other arguments, got {tuple(t.shape)}")
+        k = int(t.shape[1])
+    if nstep is None:
+        raise ValueError("nstep is required when ctrl is None")
+    nstep = int(nstep)
+    if ctrl is not None and hold >= 1 and nstep >= 1 and int(ctrl.shape[lead + 1]) != -(-nstep // int(hold)):
+        raise ValueError(f"ctrl holds {int(ctrl.shape[lead + 1])} knots, nstep = {nstep} with hold = {hold} needs "
+                         f"{-(-nstep // int(hold))}")
+    return (1 if k is None else k), nstep
+
+
+class RolloutMethods:
+    """Mixin of PhysicsBatch (uses its model, native, n, device, dtype and state)."""
+
+    @property
+    def state_size(self) -> int:
+        """nstate = 1 + nq + nv: ``[time, qpos, qvel]``."""
+        return 1 + int(self.model.nq) + int(self.model.nv)
+
+    def get_state(self) -> torch.Tensor:
+        """The envs' state vectors ``[time, qpos, qvel]``, a new tensor [N, nstate]."""
+        return torch.cat([self.time[:, None], self.qpos, self.qvel], dim=1)
+
+    def set_state(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> None:
+        """Writes ``[time, qpos, qvel]`` rows [N, nstate] into the batch (the rows of envs that
+        ``mask``, uint8 or bool [N], selects). qacc_warmstart, ctrl and the applied forces stay."""
+        nq = int(self.model.nq)
+        assert tuple(x.shape) == (self.n, self.state_size), x.shape
+        x = x.to(device=self.device, dtype=self.dtype)
+        parts = ((self.time, x[:, 0]), (self.qpos, x[:, 1:1 + nq]), (self.qvel, x[:, 1 + nq:]))
+        if mask is None:
+            for dst, src in parts:
+                dst.copy_(src)
+        else:
+            sel = mask.to(device=self.device).bool()
+            for dst, src in parts:
+                dst.copy_(torch.where(sel if dst.dim() == 1 else sel[:, None], src, dst))
+
+    def _rollout_workspace(self, slots: Optional[int], sensordata: bool, total: int):
+        if slots is None:
+            one = int(lib().mgx_rollout_bytes(self.native.handle, 1, int(sensordata)))
+            check(min(one, 0), "mgx_rollout_bytes")
+            slots = max(1, min(total, WORKSPACE_LIMIT // one))
+        slots = int(slots)
+        cache = self.__dict__.setdefault("_rollout_ws", {})
+        key = (slots, bool(sensordata))
+        if key not in cache:
+            # below one slot no workspace size is defined: the library refuses the call
+            nbytes = int(lib().mgx_rollout_bytes(self.native.handle, max(slots, 1), int(sensordata)))
+            check(min(nbytes, 0), "mgx_rollout_bytes")
+            cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return slots, cache[key]
+
+    def rollout(self, ctrl: Optional[torch.Tensor] = None, nstep: Optional[int] = None,
+                initial_state: Optional[torch.Tensor] = None, initial_warmstart: Optional[torch.Tensor] = None,
+                nsub: int = 1, hold: int = 1, shared_ctrl: bool = False, sensordata: bool = False,
+                mask: Optional[torch.Tensor] = None, stream=None, slots: Optional[int] = None,
+                only: Optional[Sequence[str]] = None, out: Optional[RolloutResult] = None) -> RolloutResult:
+        """``RolloutResult(state, sensordata, n_done)``: K open-loop rollouts of T recorded steps
+        per (masked) env, asynchronously on the stream; each recorded step is ``nsub`` mj_steps.
+
+        ``ctrl`` [N, K, ceil(T / hold), nu] (``shared_ctrl``: [K, ceil(T / hold), nu] for all envs)
+        is the raw actuator control, one knot per ``hold`` recorded steps; None holds each env's
+        current ctrl and needs ``nstep``. ``initial_state`` [N, K, nstate] / ``initial_warmstart``
+        [N, K, nv] default to each env's current state / qacc_warmstart. K and T are inferred from
+        these tensors (K = 1 when none is given). ``sensordata=True`` also records the sensors.
+        ``slots`` bounds the workspace (virtual envs held at once; default: all N K in one pass up to
+        1 GiB); the workspace is allocated once per (slots, sensordata). ``only`` names the outputs
+        wanted; rows of envs that ``mask`` (uint8 [N]) deselects are left as they were."""
+        n, m = self.n, self.model
+        nq, nv, nu = int(m.nq), int(m.nv), int(m.nu)
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.numel() == n and mask.is_cuda and mask.is_contiguous()
+        want = [f for f in ROLLOUT_OUTPUTS if sensordata or f != "sensordata"] if only is None else list(only)
+        for f in want:
+            if f not in ROLLOUT_OUTPUTS:
+                raise KeyError(f"unknown rollout output {f!r}; there are {list(ROLLOUT_OUTPUTS)}")
+        sensordata = "sensordata" in want
+        k, t = rollout_shape(n, nu, ctrl, nstep, initial_state, initial_warmstart, hold, shared_ctrl)
+        for name, x, width in (("ctrl", ctrl, nu), ("initial_state", initial_state, self.state_size),
+                               ("initial_warmstart", initial_warmstart, nv)):
+            if x is not None:
+                assert x.dtype == self.dtype and x.is_cuda and x.is_contiguous() and x.shape[-1] == width, name
+        nsd = int(m.nsensordata)
+        if sensordata:
+            self._sensor_ready()
+        if out is None:
+            cache = self.__dict__.setdefault("_rollout_out", {})
+            key = (k, t, sensordata)
+            if key not in cache and k >= 1 and t >= 1:
+                cache[key] = alloc_rollout(n, k, t, 1 + nq + nv, nsd, self.dtype, self.device, sensordata)
+            out = cache.get(key) or RolloutResult()
+        slots, ws = self._rollout_workspace(slots, sensordata, max(n * k, 1))
+        io = cabi.MgxRolloutIO()
+        io.n_roll, io.n_step, io.nsub, io.hold = k, t, int(nsub), int(hold)
+        io.flags = cabi.MGX_ROLLOUT_SHARED_CTRL if shared_ctrl else 0
+        io.slots, io.workspace, io.workspace_bytes = slots, ws.data_ptr(), ws.numel()
+        io.initial_state = None if initial_state is None else initial_state.data_ptr()
+        io.initial_warmstart = None if initial_warmstart is None else initial_warmstart.data_ptr()
+        io.ctrl = None if ctrl is None or nu == 0 else ctrl.data_ptr()
+        res = RolloutResult()
+        widths = {"state": (k, t, 1 + nq + nv), "sensordata": (k, t, nsd), "n_done": (k,)}
+        for f in want:
+            x = getattr(out, f)
+            if x is None:
+                continue  # bad K / T: the library names the argument
+            assert x.is_contiguous() and tuple(x.shape) == (n,) + widths[f], (f, tuple(x.shape))
+            assert x.dtype == (torch.int32 if f == "n_done" else self.dtype)
+            # a model without sensors has no bytes to write; the request still reaches the library,
+            # which refuses it for the models mgx_forward refuses
+            setattr(io, f, x.data_ptr() or ws.data_ptr())
+            setattr(res, f, x)
+        check(lib().mgx_rollout(self.native.handle, C.byref(self._state), C.byref(io), n, _ptr(mask),
+                                _stream(stream)), "mgx_rollout")
+        return res
+
+
+class RolloutForwarding:
+    """Mixin of the ``*VectorEnv`` classes: the batch's open-loop rollouts under the env's name.
+
+    The method is ``physics_rollout``: ``rollout`` on an env is its tensor of running episode sums.
+    ``ctrl`` is the RAW ACTUATOR CONTROL of the physics model (``batch.ctrl``), not the task's
+    action: the env's action clipping / scaling and its scripted actuators (goalkeeper, obstacle
+    motors ...) are not applied, and no reward, observation or termination is computed. Pass
+    ``nsub`` = the env's frame skip (10 for parkour and assembly, 1 otherwise) for one recorded step
+    to span the physics of one env step."""
+
+    @property
+    def state_size(self) -> int:
+        return self.batch.state_size
+
+    def get_state(self):
+        return self.batch.get_state()
+
+    def set_state(self, x, mask=None):
+        return self.batch.set_state(x, mask=mask)
+
+    def physics_rollout(self, **kw):
+        """PhysicsBatch.rollout of this env's batch (raw actuator ctrl; ``nsub`` = frame skip)."""
+        return self.batch.rollout(**kw)

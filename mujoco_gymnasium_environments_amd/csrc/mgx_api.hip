@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
@@ -20,15 +20,13 @@ MGX_PROF_SETTER(mgx_prof_set_buffer)
 
 namespace {
 thread_local std::string g_err;
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIPCHK(x) MGX_HIPCHK(x)
 }  // namespace
 
 namespace mgx {
-int host_fail(int code, const std::string& msg) { return fail(code, msg); }
+int host_fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
 }  // namespace mgx
 
 // ------------------------------------------------------------------------- kernels
@@ -457,7 +455,7 @@ int build_model(const mgx_model_desc* d, int device, mgx_model* out, DevModel<T>
   for (int b = 1; b < nb; b++) {
     std::vector<int> path;
     for (int i = b; i > 0; i = d->body_parentid[i]) path.push_back(i);
-    if ((int)path.size() > MGX_MAX_DEPTH) return fail(MGX_E_CAPACITY, "body tree deeper than MGX_MAX_DEPTH");
+    if ((int)path.size() > MGX_MAX_DEPTH) return host_fail(MGX_E_CAPACITY, "body tree deeper than MGX_MAX_DEPTH");
     depth[b] = (int)path.size();
     for (int c = 0; c < depth[b]; c++) chain[b * MGX_MAX_DEPTH + c] = path[depth[b] - 1 - c];
   }
@@ -466,7 +464,7 @@ int build_model(const mgx_model_desc* d, int device, mgx_model* out, DevModel<T>
   for (int k = 0; k < nv; k++) {
     int t = 0;
     for (int j = k; j >= 0; j = d->dof_parentid[j], t++) {
-      if (t >= MGX_MAX_DEPTH) return fail(MGX_E_CAPACITY, "dof chain longer than MGX_MAX_DEPTH");
+      if (t >= MGX_MAX_DEPTH) return host_fail(MGX_E_CAPACITY, "dof chain longer than MGX_MAX_DEPTH");
       anc[k * MGX_MAX_DEPTH + t] = j;
       ancadr[k * MGX_MAX_DEPTH + t] = d->dof_Madr[j];
       if (j != k) {
@@ -544,25 +542,35 @@ int build_model(const mgx_model_desc* d, int device, mgx_model* out, DevModel<T>
   B.reals(d->actuator_forcerange, 2 * nu, &M.actuator_forcerange);
   B.reals(d->actuator_gainprm, 3 * nu, &M.actuator_gainprm); B.reals(d->actuator_biasprm, 3 * nu, &M.actuator_biasprm);
   B.reals(d->qpos0, d->nq, &M.qpos0); B.reals(d->qpos_spring, d->nq, &M.qpos_spring);
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipMalloc(&out->dbuf, B.host.size()));
-  HIPCHK(hipMemcpy(out->dbuf, B.host.data(), B.host.size(), hipMemcpyHostToDevice));
+  MGX_HIPCHK(hipSetDevice(device));
+  MGX_HIPCHK(hipMalloc(&out->dbuf, B.host.size()));
+  MGX_HIPCHK(hipMemcpy(out->dbuf, B.host.data(), B.host.size(), hipMemcpyHostToDevice));
   out->dbytes = B.host.size();
   for (auto& f : B.fix) *f.second = (char*)out->dbuf + f.first;
   return MGX_OK;
 }
 
-template <typename KernelT>
-int set_lds(KernelT k, int bytes) { return mgx_set_lds(k, bytes); }
+// every buffer the soccer kernels dereference unguarded (flags, rollout and episode are optional)
+bool soccer_env_ok(const mgx_soccer_env* e) {
+  return e->prev_ball_pos && e->prev_robot_pos && e->wind && e->step && e->goal_scored && e->stats;
+}
 
-int check_state(const mgx_state* s) { return mgx::host_check_state(s); }
+constexpr Task<mgx_soccer_env> kTask{"soccer", "soccer", &mgx_model::soccer_ok, soccer_env_ok, false};
+// rows in LDS only (mgx_soccer_configure refuses the others): one kernel per MODE, named in both row placements
+template <typename T>
+constexpr auto kKernels = task_kernels(k_soccer<T, 0>, k_soccer<T, 0>, k_soccer<T, 1>, k_soccer<T, 1>, k_soccer_logic<T>);
 
 }  // namespace
 
 namespace mgx {
 int host_check_state(const mgx_state* s) {
   if (!s || !s->qpos || !s->qvel || !s->qacc_warmstart || !s->ctrl || !s->qfrc_applied || !s->xfrc_applied || !s->time)
-    return fail(MGX_E_ARG, "null state buffer");
+    return host_fail(MGX_E_ARG, "null state buffer");
+  return MGX_OK;
+}
+int host_check_scratch(const mgx_model* m, const mgx_state* s) {
+  if (m->L.gB && !s->scratch)
+    return host_fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
   return MGX_OK;
 }
 }  // namespace mgx
@@ -878,7 +886,7 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   Pipe P;
   int banks = autoreset ? e->banks : 0;
   size_t need = make_pipe(m, e->workspace, n_env, e->banks, &P);
-  if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
+  if (e->workspace_bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
   int slots = n_env * (1 + banks);
   const Hooks& H = m->hooks;
   // occupancy probe: MGX_ROWS_LDS pads the row builder's LDS (fewer waves per CU; up to 64 KiB)
@@ -941,42 +949,42 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
     if (P.hmain) mlds = std::max(mlds, pgs_lds_bytes(m, P.maxE, 1));
     if (P.split_blocks) mlds = std::max(mlds, staged_pgs_lds_bytes(m, P.maxE, 64, 0, mgx_twl(false)));
     if (H.pgs_lds_pad > mlds && H.pgs_lds_pad <= 96 * 1024) mlds = H.pgs_lds_pad;
-    HIPCHK(hipEventRecord(bs->entry, st));
+    MGX_HIPCHK(hipEventRecord(bs->entry, st));
     launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, 0, n_env, rlds, st);
     if (tail) {
-      HIPCHK(hipEventRecord(tail->rows, st));
-      HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
+      MGX_HIPCHK(hipEventRecord(tail->rows, st));
+      MGX_HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
       launch_pgs<T>(P, n_env, mlds, tail->s, M.iterations, M.tolerance, scale, 0, H, 1);
-      HIPCHK(hipEventRecord(tail->big, tail->s));
+      MGX_HIPCHK(hipEventRecord(tail->big, tail->s));
     }
-    HIPCHK(hipStreamWaitEvent(bs->s, bs->entry, 0));
+    MGX_HIPCHK(hipStreamWaitEvent(bs->s, bs->entry, 0));
     launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, nullptr, B, banks, nbank, rlds, bs->s, n_env);
-    if (bmode == 2) HIPCHK(hipEventRecord(bs->rows, bs->s));
+    if (bmode == 2) MGX_HIPCHK(hipEventRecord(bs->rows, bs->s));
     launch_pgs<T>(B, nbank, mlds, bs->s, M.iterations, M.tolerance, scale, 0, H);
     if (bmode == 1) {
       launch_soccer_bank_finish<T>(Mf, ids, n_env, B, 1, m->Lf.bytes, bs->s);
-      HIPCHK(hipEventRecord(bs->done, bs->s));
+      MGX_HIPCHK(hipEventRecord(bs->done, bs->s));
     }
     launch_pgs<T>(P, n_env, mlds, st, M.iterations, M.tolerance, scale, 0, H, tail ? 2 : 0);
     if (tail) {
       launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                               env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, 1);
-      HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
+      MGX_HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
     }
-    HIPCHK(hipStreamWaitEvent(st, bmode == 1 ? bs->done : bs->rows, 0));
+    MGX_HIPCHK(hipStreamWaitEvent(st, bmode == 1 ? bs->done : bs->rows, 0));
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                             env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, tail ? 2 : 0);
     int fgrid = n_env < 256 ? n_env : 256;
     launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
                             SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
     if (bmode == 2) {
-      HIPCHK(hipEventRecord(bs->live, st));
-      HIPCHK(hipStreamWaitEvent(bs->s, bs->live, 0));
+      MGX_HIPCHK(hipEventRecord(bs->live, st));
+      MGX_HIPCHK(hipStreamWaitEvent(bs->s, bs->live, 0));
       launch_soccer_bank_finish<T>(Mf, ids, n_env, B, 1, m->Lf.bytes, bs->s);
-      HIPCHK(hipEventRecord(bs->done, bs->s));
-      HIPCHK(hipStreamWaitEvent(st, bs->done, 0));
+      MGX_HIPCHK(hipEventRecord(bs->done, bs->s));
+      MGX_HIPCHK(hipStreamWaitEvent(st, bs->done, 0));
     }
-    HIPCHK(hipGetLastError());
+    MGX_HIPCHK(hipGetLastError());
     return MGX_OK;
   }
   launch_soccer_rows<T>(Ms, ids, *s, *e, action, n_env, mask, P, banks, slots, rlds, st);
@@ -996,32 +1004,32 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   if (tail) {
     // the tail finisher on one solver list (live and bank slots): the heavy slots of either kind on
     // the side stream, tier A beside them, then the bank finisher and tier B
-    HIPCHK(hipEventRecord(tail->rows, st));
-    HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
+    MGX_HIPCHK(hipEventRecord(tail->rows, st));
+    MGX_HIPCHK(hipStreamWaitEvent(tail->s, tail->rows, 0));
     launch_pgs<T>(P, slots, mlds, tail->s, M.iterations, M.tolerance, scale, 0, H, 1);
-    HIPCHK(hipEventRecord(tail->big, tail->s));
+    MGX_HIPCHK(hipEventRecord(tail->big, tail->s));
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H, 2);
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                             env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, 1);
-    HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
+    MGX_HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                             env_offset, n_env, mask, P, banks, m->Lf.bytes, st, true, 2);
     int fgrid = n_env < 256 ? n_env : 256;
     launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
                             SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
-    HIPCHK(hipGetLastError());
+    MGX_HIPCHK(hipGetLastError());
     return MGX_OK;
   }
   if (!H.pgs_lds_b && (P.maxE <= P.capE || P.hmain || P.split_blocks)) {
     // every slot fits the main launch (the default capacity): no wide launch at all
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H);
   } else if (SideStream* side = (!H.pgs_lds_b && H.side_stream) ? side_stream(st) : nullptr) {
-    HIPCHK(hipEventRecord(side->rows, st));
-    HIPCHK(hipStreamWaitEvent(side->s, side->rows, 0));
+    MGX_HIPCHK(hipEventRecord(side->rows, st));
+    MGX_HIPCHK(hipStreamWaitEvent(side->s, side->rows, 0));
     launch_pgs<T>(P, wgrid, wlds, side->s, M.iterations, M.tolerance, scale, 1, H);
-    HIPCHK(hipEventRecord(side->big, side->s));
+    MGX_HIPCHK(hipEventRecord(side->big, side->s));
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H);
-    HIPCHK(hipStreamWaitEvent(st, side->big, 0));
+    MGX_HIPCHK(hipStreamWaitEvent(st, side->big, 0));
   } else {
     launch_pgs<T>(P, slots, mlds, st, M.iterations, M.tolerance, scale, 0, H);
     launch_pgs<T>(P, wgrid, wlds, st, M.iterations, M.tolerance, scale, 1, H);
@@ -1033,7 +1041,7 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
   int fgrid = n_env < 256 ? n_env : 256;
   launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P, SETTLE_FIXUP,
                           fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
-  HIPCHK(hipGetLastError());
+  MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
 }
 
@@ -1046,11 +1054,11 @@ static int soccer_reset_staged(const mgx_model* m, const DevModel<T>& M, const D
                                float* obs, uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
   size_t need = make_pipe(m, e->workspace, n_env, e->banks, &P);
-  if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
+  if (e->workspace_bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
   T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
   launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, draws, obs, seed, env_offset, n_env, mask, P, SETTLE_RESET, n_env,
                           settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
-  HIPCHK(hipGetLastError());
+  MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
 }
 
@@ -1078,18 +1086,18 @@ const char* mgx_last_error(void) { return g_err.c_str(); }
 int mgx_abi_version(void) { return MGX_ABI_VERSION; }
 
 int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_model** out) {
-  if (!d || !out) return fail(MGX_E_ARG, "null argument");
-  if (precision != MGX_F32 && precision != MGX_F64) return fail(MGX_E_ARG, "precision must be MGX_F32 or MGX_F64");
+  if (!d || !out) return host_fail(MGX_E_ARG, "null argument");
+  if (precision != MGX_F32 && precision != MGX_F64) return host_fail(MGX_E_ARG, "precision must be MGX_F32 or MGX_F64");
   // nv <= 64: one dof per lane (every task kernel); 64 < nv <= 128: the wide kernels only
   // (mgx_wide.h, two dofs per lane: humanoid_construction, nv 99), which every other configure
   // entry point refuses
-  if (d->nv > MGX_MAX_NV_WIDE) return fail(MGX_E_CAPACITY, "nv > 128 not supported by the wave-per-env kernels");
+  if (d->nv > MGX_MAX_NV_WIDE) return host_fail(MGX_E_CAPACITY, "nv > 128 not supported by the wave-per-env kernels");
   if (d->nbody > 4096 || (d->solver != 0 && d->solver != 2) || (d->integrator != 0 && d->integrator != 1))
-    return fail(MGX_E_UNSUPPORTED, "this build implements PGS or Newton with Euler or RK4");
+    return host_fail(MGX_E_UNSUPPORTED, "this build implements PGS or Newton with Euler or RK4");
   bool condim13 = true;  // the staged row builder packs one contact per 4-row block
   for (int p = 0; p < d->npair; p++) {
     const int c = d->pair_condim[p];
-    if (c != 1 && c != 3 && c != 4 && c != 6) return fail(MGX_E_UNSUPPORTED, "condim must be 1, 3, 4 or 6");
+    if (c != 1 && c != 3 && c != 4 && c != 6) return host_fail(MGX_E_UNSUPPORTED, "condim must be 1, 3, 4 or 6");
     condim13 = condim13 && (c == 1 || c == 3);
   }
   mgx_model* m = new mgx_model();
@@ -1105,16 +1113,16 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
   int max_nefc = d->efc_capacity > 0 ? d->efc_capacity : 192;
   int max_ncon = d->con_capacity > 0 ? d->con_capacity : 64;
   if (const char* v = getenv("MGX_MAX_NEFC")) {
-    if (atoi(v) < max_nefc) { delete m; return fail(MGX_E_ARG, "MGX_MAX_NEFC below the model's row capacity"); }
+    if (atoi(v) < max_nefc) { delete m; return host_fail(MGX_E_ARG, "MGX_MAX_NEFC below the model's row capacity"); }
     max_nefc = atoi(v);
   }
   if (const char* v = getenv("MGX_MAX_NCON")) {
-    if (atoi(v) < max_ncon) { delete m; return fail(MGX_E_ARG, "MGX_MAX_NCON below the model's contact capacity"); }
+    if (atoi(v) < max_ncon) { delete m; return host_fail(MGX_E_ARG, "MGX_MAX_NCON below the model's contact capacity"); }
     max_ncon = atoi(v);
   }
-  if (max_nefc > 1024 || max_ncon > 512) { delete m; return fail(MGX_E_CAPACITY, "capacity above 1024 rows / 512 contacts"); }
+  if (max_nefc > 1024 || max_ncon > 512) { delete m; return host_fail(MGX_E_CAPACITY, "capacity above 1024 rows / 512 contacts"); }
   max_nefc = (max_nefc + 3) & ~3;  // the staged solver sweeps rows in blocks of 4
-  if (max_nefc < 4 || max_ncon < 1) { delete m; return fail(MGX_E_ARG, "row / contact capacity too small"); }
+  if (max_nefc < 4 || max_ncon < 1) { delete m; return host_fail(MGX_E_ARG, "row / contact capacity too small"); }
   int rb = precision == MGX_F32 ? 4 : 8;
   // broadphase survivor list: 128 for the small candidate sets (soccer 251, parkour 48 pairs),
   // up to 768 for large ones (bipedal 3185 pairs)
@@ -1158,7 +1166,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
     m->md.L = m->L; m->mds = m->md; m->mds.L = m->Ls; m->mdf = m->md; m->mdf.L = m->Lf;
   }
   if (rc != MGX_OK) { delete m; return rc; }
-  if (m->L.bytes > 160 * 1024) { delete m; return fail(MGX_E_CAPACITY, "per-env LDS exceeds 160 KiB"); }
+  if (m->L.bytes > 160 * 1024) { delete m; return host_fail(MGX_E_CAPACITY, "per-env LDS exceeds 160 KiB"); }
   int r2 = step_kernels_configure(m);
   if (r2 != MGX_OK) { delete m; return r2; }
   r2 = forward_kernels_configure(m);
@@ -1169,11 +1177,9 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
     r2 = wide_kernels_configure(m);
     if (r2 != MGX_OK) { delete m; return r2; }
   }
-  r2 = precision == MGX_F32
-               ? (set_lds(k_soccer<float, 0>, m->L.bytes) | set_lds(k_soccer<float, 1>, m->L.bytes) |
-                  set_lds(k_soccer_logic<float>, m->L.bytes) | set_lds(k_soccer_template<float>, m->L.bytes))
-               : (set_lds(k_soccer<double, 0>, m->L.bytes) | set_lds(k_soccer<double, 1>, m->L.bytes) |
-                  set_lds(k_soccer_logic<double>, m->L.bytes) | set_lds(k_soccer_template<double>, m->L.bytes));
+  r2 = task_configure_lds(m, kKernels<float>, kKernels<double>) |
+       (precision == MGX_F32 ? mgx_set_lds(k_soccer_template<float>, m->L.bytes)
+                             : mgx_set_lds(k_soccer_template<double>, m->L.bytes));
   if (r2 != MGX_OK) { delete m; return r2; }
   if (m->staged_ok) {
     int sl = pgs_lds_bytes(m, m->Ls.max_nefc);  // the settle kernel's (settle_lds_bytes)
@@ -1183,7 +1189,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
     if (r2 != MGX_OK) { delete m; return r2; }
     int pl = pgs_lds_bytes(m, m->Ls.max_nefc);  // the global-B launch's
     if (pl < 96 * 1024) pl = 96 * 1024;  // the arena (MGX_PGS_ARENA tuning up to 96 KiB)
-    if (pl > 160 * 1024) { delete m; return fail(MGX_E_CAPACITY, "solver LDS exceeds 160 KiB: lower MGX_MAX_NEFC"); }
+    if (pl > 160 * 1024) { delete m; return host_fail(MGX_E_CAPACITY, "solver LDS exceeds 160 KiB: lower MGX_MAX_NEFC"); }
     int r3 = pgs_configure_lds(precision, pl, wide_arena_bytes(m) + 64);
     if (r3 != MGX_OK) { delete m; return r3; }
   }
@@ -1201,7 +1207,7 @@ int mgx_model_destroy(mgx_model* m) {
 }
 
 int mgx_model_get_info(const mgx_model* m, mgx_model_info* o) {
-  if (!m || !o) return fail(MGX_E_ARG, "null argument");
+  if (!m || !o) return host_fail(MGX_E_ARG, "null argument");
   int nq, nv, nu, nb, nj, ng;
   if (m->precision == MGX_F32) { nq = m->mf.nq; nv = m->mf.nv; nu = m->mf.nu; nb = m->mf.nbody; nj = m->mf.njnt; ng = m->mf.ngeom; }
   else { nq = m->md.nq; nv = m->md.nv; nu = m->md.nu; nb = m->md.nbody; nj = m->md.njnt; ng = m->md.ngeom; }
@@ -1214,13 +1220,13 @@ int mgx_model_get_info(const mgx_model* m, mgx_model_info* o) {
 }
 
 int mgx_soccer_configure(mgx_model* m, const mgx_soccer_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   if (m->L.gB || (m->precision == MGX_F32 ? m->mf.integrator : m->md.integrator) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the soccer kernels need an Euler model whose rows fit LDS");
+    return host_fail(MGX_E_UNSUPPORTED, "the soccer kernels need an Euler model whose rows fit LDS");
   if ((m->precision == MGX_F32 ? m->mf.solver : m->md.solver) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the soccer kernels solve with PGS (soccer_env.py:150-151)");
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
+    return host_fail(MGX_E_UNSUPPORTED, "the soccer kernels solve with PGS (soccer_env.py:150-151)");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
   if (m->precision == MGX_F32) fill_ids(m->sf, ids, m->mf, nullptr);
   else fill_ids(m->sd, ids, m->md, nullptr);
   m->soccer_ok = true;
@@ -1231,7 +1237,7 @@ int mgx_soccer_configure(mgx_model* m, const mgx_soccer_ids* ids) {
 int mgx_soccer_configure_reset(mgx_model* m, int root_qposadr, int n_noise, const int32_t* noise_qposadr,
                                const double* noise_range) {
   if (!m || n_noise < 0 || n_noise > 29 || (n_noise && (!noise_qposadr || !noise_range)))
-    return fail(MGX_E_ARG, "bad reset table");
+    return host_fail(MGX_E_ARG, "bad reset table");
   auto fill = [&](auto& o) {
     o.root_qposadr = root_qposadr;
     o.n_noise = n_noise;
@@ -1248,76 +1254,48 @@ int mgx_soccer_configure_reset(mgx_model* m, int root_qposadr, int n_noise, cons
 int mgx_soccer_step(const mgx_model* m, const mgx_state* s, const mgx_soccer_env* e, const float* action, float* obs,
                     double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                     uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->soccer_ok) return fail(MGX_E_ARG, "mgx_soccer_configure not called");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  int rc = check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace) {
-    if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
-    if (e->banks < 0 || e->banks > 16) return fail(MGX_E_ARG, "banks must be in [0, 16]");
+    if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
+    if (e->banks < 0 || e->banks > 16) return host_fail(MGX_E_ARG, "banks must be in [0, 16]");
     if (m->precision == MGX_F32)
       return soccer_step_staged<float>(m, m->mf, m->mfs, m->mff, m->sf, s, e, action, obs, reward, terminated,
                                        truncated, final_obs, autoreset, seed, env_offset, n_env, mask, st);
     return soccer_step_staged<double>(m, m->md, m->mds, m->mdf, m->sd, s, e, action, obs, reward, terminated, truncated,
                                       final_obs, autoreset, seed, env_offset, n_env, mask, st);
   }
-  Pipe none{};
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL((k_soccer<float, 0>), dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->sf, *s, *e, action,
-                       (const float*)nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                       env_offset, n_env, mask, none, 0);
-  else
-    hipLaunchKernelGGL((k_soccer<double, 0>), dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->sd, *s, *e, action,
-                       (const double*)nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                       env_offset, n_env, mask, none, 0);
-  HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->sf, m->sd, 0, n_env, st, *e, action, RealPtr{nullptr},
+                     obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env, mask, Pipe{}, 0);
 }
 
 int mgx_soccer_reset(const mgx_model* m, const mgx_state* s, const mgx_soccer_env* e, const void* draws, float* obs,
                      uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->soccer_ok) return fail(MGX_E_ARG, "mgx_soccer_configure not called");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  int rc = check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace) {
-    if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
-    if (e->banks < 0 || e->banks > 16) return fail(MGX_E_ARG, "banks must be in [0, 16]");
+    if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
+    if (e->banks < 0 || e->banks > 16) return host_fail(MGX_E_ARG, "banks must be in [0, 16]");
     if (m->precision == MGX_F32)
       return soccer_reset_staged<float>(m, m->mf, m->mfs, m->mff, m->sf, s, e, (const float*)draws, obs, seed,
                                         env_offset, n_env, mask, st);
     return soccer_reset_staged<double>(m, m->md, m->mds, m->mdf, m->sd, s, e, (const double*)draws, obs, seed,
                                        env_offset, n_env, mask, st);
   }
-  Pipe none{};
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL((k_soccer<float, 1>), dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->sf, *s, *e,
-                       (const float*)nullptr, (const float*)draws, obs, (double*)nullptr, (uint8_t*)nullptr,
-                       (uint8_t*)nullptr, (float*)nullptr, 0, seed, env_offset, n_env, mask, none, 0);
-  else
-    hipLaunchKernelGGL((k_soccer<double, 1>), dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->sd, *s, *e,
-                       (const float*)nullptr, (const double*)draws, obs, (double*)nullptr, (uint8_t*)nullptr,
-                       (uint8_t*)nullptr, (float*)nullptr, 0, seed, env_offset, n_env, mask, none, 0);
-  HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->sf, m->sd, 1, n_env, st, *e, nullptr, RealPtr{draws},
+                     obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask, Pipe{}, 0);
 }
 
 int64_t mgx_soccer_workspace_bytes(const mgx_model* m, int n_env, int banks) {
-  if (!m || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
+  if (!m || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
+  if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
   return (int64_t)make_pipe(m, nullptr, n_env, banks, nullptr);
 }
 
 int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_t* out, int n_out) {
-  if (!m || !out || n_env <= 0 || banks < 0 || banks > 16 || n_out < 10) return fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_ok) return fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
+  if (!m || !out || n_env <= 0 || banks < 0 || banks > 16 || n_out < 10) return host_fail(MGX_E_ARG, "bad argument");
+  if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
   Pipe P;
   make_pipe(m, nullptr, n_env, banks, &P);
   // [11], [12]: the bank view's counter block and arrival list (MGX_BANK_STREAM); [13], [14]: the
@@ -1330,34 +1308,28 @@ int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_
 }
 
 int mgx_soccer_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks, void* stream) {
-  if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
+  if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
   Pipe P;
   size_t need = make_pipe(m, workspace, n_env, banks, &P);
-  if (bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
+  if (bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
   hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemsetAsync(workspace, 0, need, st));
+  MGX_HIPCHK(hipMemsetAsync(workspace, 0, need, st));
   size_t nb = (size_t)n_env * (banks > 0 ? banks : 1);
-  HIPCHK(hipMemsetAsync(P.base + P.o_bk, 0xFF, nb * 4, st));  // bank settle counters = -1 (empty)
+  MGX_HIPCHK(hipMemsetAsync(P.base + P.o_bk, 0xFF, nb * 4, st));  // bank settle counters = -1 (empty)
   if (m->precision == MGX_F32)
     hipLaunchKernelGGL(k_soccer_template<float>, dim3(1), dim3(64), m->L.bytes, st, m->mf, P);
   else
     hipLaunchKernelGGL(k_soccer_template<double>, dim3(1), dim3(64), m->L.bytes, st, m->md, P);
-  HIPCHK(hipGetLastError());
+  MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
 }
 
 int mgx_soccer_logic_test(const mgx_model* m, const mgx_soccer_logic_io* io, int n_env, void* stream) {
-  if (!m || !io) return fail(MGX_E_ARG, "null argument");
-  if (!m->soccer_ok) return fail(MGX_E_ARG, "mgx_soccer_configure not called");
-  if (io->max_contacts > m->L.max_ncon) return fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
+  if (!m || !io) return host_fail(MGX_E_ARG, "null argument");
+  if (!m->soccer_ok) return host_fail(MGX_E_ARG, "mgx_soccer_configure not called");
+  if (io->max_contacts > m->L.max_ncon) return host_fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_soccer_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->sf, *io, n_env);
-  else
-    hipLaunchKernelGGL(k_soccer_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->sd, *io, n_env);
-  HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->sf, m->sd, n_env, (hipStream_t)stream, *io, n_env);
 }
 
 }  // extern "C"

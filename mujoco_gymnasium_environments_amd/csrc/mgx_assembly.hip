@@ -10,7 +10,7 @@
 // task state / reward / termination / observation, with same-step autoreset (10 settle steps),
 // all in one launch.
 #define MGX_TEAM  // kernels with a Newton helper wave (lane_id, team_begin)
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 #include "mgx_assembly.h"
 
 using namespace mgx;
@@ -18,8 +18,6 @@ using namespace mgx;
 MGX_PROF_SETTER(mgx_prof_set_buffer_assembly)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 template <typename T, bool GB>
 __device__ __forceinline__ void bind(const DevModel<T>& m, Env<T>& e, char* smem, const mgx_state& s, int env) {
@@ -118,60 +116,36 @@ __global__ void __launch_bounds__(64) k_assembly_logic(DevModel<T> m, mgx_assemb
 
 bool assembly_env_ok(const mgx_assembly_env* e) { return e->ints && e->cumulative && e->reset_qpos; }
 
+// the kernel guards the episode counter, so autoreset runs without one
+constexpr Task<mgx_assembly_env> kTask{"assembly", "assembly", &mgx_model::assembly_ok, assembly_env_ok, true};
 template <typename T>
-int configure_lds(const mgx_model* m) {
-  return mgx_set_lds(k_assembly<T, 0, true>, m->L.bytes) | mgx_set_lds(k_assembly<T, 1, true>, m->L.bytes) |
-         mgx_set_lds(k_assembly<T, 0, false>, m->L.bytes) | mgx_set_lds(k_assembly<T, 1, false>, m->L.bytes) |
-         mgx_set_lds(k_assembly_logic<T>, m->L.bytes);
-}
-
-template <typename T, int MODE>
-void launch(const mgx_model* m, const DevModel<T>& M, const mgx_state* s, const mgx_assembly_env* e, const float* action,
-            float* obs, double* reward, uint8_t* term, uint8_t* trunc, float* final_obs, int autoreset, int n_env,
-            const uint8_t* mask, hipStream_t st) {
-  if (m->L.gB)
-    hipLaunchKernelGGL((k_assembly<T, MODE, true>), dim3(n_env), dim3(kTeamThreads), m->L.bytes, st, M, m->as, *s, *e, action,
-                       obs, reward, term, trunc, final_obs, autoreset, n_env, mask);
-  else
-    hipLaunchKernelGGL((k_assembly<T, MODE, false>), dim3(n_env), dim3(kTeamThreads), m->L.bytes, st, M, m->as, *s, *e, action,
-                       obs, reward, term, trunc, final_obs, autoreset, n_env, mask);
-}
-
-int check_common(const mgx_model* m, const mgx_state* s, const mgx_assembly_env* e) {
-  if (!m->assembly_ok) return fail(MGX_E_ARG, "mgx_assembly_configure not called");
-  if (!assembly_env_ok(e)) return fail(MGX_E_ARG, "null assembly env buffer");
-  if (s) {
-    const int rc = host_check_state(s);
-    if (rc) return rc;
-    if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  }
-  return MGX_OK;
-}
+constexpr auto kKernels = task_kernels(k_assembly<T, 0, false>, k_assembly<T, 0, true>, k_assembly<T, 1, false>,
+                                       k_assembly<T, 1, true>, k_assembly_logic<T>, kTeamThreads, kTeamThreads);
 
 }  // namespace
 
 extern "C" {
 
 int mgx_assembly_configure(mgx_model* m, const mgx_assembly_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   const bool f32 = m->precision == MGX_F32;
   const int nq = f32 ? m->mf.nq : m->md.nq, nu = f32 ? m->mf.nu : m->md.nu;
   const int nb = f32 ? m->mf.nbody : m->md.nbody, ng = f32 ? m->mf.ngeom : m->md.ngeom;
   if ((f32 ? m->mf.integrator : m->md.integrator) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the assembly kernels integrate with Euler (complete_model.xml:4)");
+    return host_fail(MGX_E_UNSUPPORTED, "the assembly kernels integrate with Euler (complete_model.xml:4)");
   if ((f32 ? m->mf.solver : m->md.solver) != 2)
-    return fail(MGX_E_UNSUPPORTED, "the assembly kernels solve with Newton (complete_model.xml:4)");
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
-  if (ids->substeps < 1 || ids->settle_steps < 0) return fail(MGX_E_ARG, "substeps must be >= 1, settle_steps >= 0");
-  if (nu != 9 || nq < 9) return fail(MGX_E_ARG, "assembly needs 9 actuators (7 motors, 2 finger servos) and nq >= 9");
-  if (ids->n_geom != ng || ng > MGX_ASSEMBLY_MAX_GEOM) return fail(MGX_E_ARG, "n_geom must equal ngeom (<= 128)");
-  if (ids->ee_body < 0 || ids->ee_body >= nb) return fail(MGX_E_ARG, "ee_site body id out of range");
+    return host_fail(MGX_E_UNSUPPORTED, "the assembly kernels solve with Newton (complete_model.xml:4)");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->substeps < 1 || ids->settle_steps < 0) return host_fail(MGX_E_ARG, "substeps must be >= 1, settle_steps >= 0");
+  if (nu != 9 || nq < 9) return host_fail(MGX_E_ARG, "assembly needs 9 actuators (7 motors, 2 finger servos) and nq >= 9");
+  if (ids->n_geom != ng || ng > MGX_ASSEMBLY_MAX_GEOM) return host_fail(MGX_E_ARG, "n_geom must equal ngeom (<= 128)");
+  if (ids->ee_body < 0 || ids->ee_body >= nb) return host_fail(MGX_E_ARG, "ee_site body id out of range");
   for (int c = 0; c < MGX_ASSEMBLY_NCOMP; c++)
-    if (ids->comp_body[c] < 0 || ids->comp_body[c] >= nb) return fail(MGX_E_ARG, "component body id out of range");
+    if (ids->comp_body[c] < 0 || ids->comp_body[c] >= nb) return host_fail(MGX_E_ARG, "component body id out of range");
   for (int g = 0; g < ng; g++)
-    if (ids->geom_comp[g] < -1 || ids->geom_comp[g] >= MGX_ASSEMBLY_NCOMP) return fail(MGX_E_ARG, "geom_comp out of range");
-  const int rc = f32 ? configure_lds<float>(m) : configure_lds<double>(m);
+    if (ids->geom_comp[g] < -1 || ids->geom_comp[g] >= MGX_ASSEMBLY_NCOMP) return host_fail(MGX_E_ARG, "geom_comp out of range");
+  const int rc = task_configure_lds(m, kKernels<float>, kKernels<double>);
   if (rc != MGX_OK) return rc;
   m->as = *ids;
   m->assembly_ok = true;
@@ -181,49 +155,26 @@ int mgx_assembly_configure(mgx_model* m, const mgx_assembly_ids* ids) {
 int mgx_assembly_step(const mgx_model* m, const mgx_state* s, const mgx_assembly_env* e, const float* action, float* obs,
                       double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                       int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !s || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  const int rc = check_common(m, s, e);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 0>(m, m->mf, s, e, action, obs, reward, terminated, truncated, final_obs, autoreset, n_env, mask, st);
-  else
-    launch<double, 0>(m, m->md, s, e, action, obs, reward, terminated, truncated, final_obs, autoreset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, s && action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->as, m->as, 0, n_env, (hipStream_t)stream, *e, action,
+                     obs, reward, terminated, truncated, final_obs, autoreset, n_env, mask);
 }
 
 int mgx_assembly_reset(const mgx_model* m, const mgx_state* s, const mgx_assembly_env* e, float* obs, int n_env,
                        const uint8_t* mask, void* stream) {
-  if (!m || !s || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  const int rc = check_common(m, s, e);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 1>(m, m->mf, s, e, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, n_env, mask, st);
-  else
-    launch<double, 1>(m, m->md, s, e, nullptr, obs, nullptr, nullptr, nullptr, nullptr, 0, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, s && obs, false, n_env)) return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->as, m->as, 1, n_env, (hipStream_t)stream, *e, nullptr,
+                     obs, nullptr, nullptr, nullptr, nullptr, 0, n_env, mask);
 }
 
 int mgx_assembly_logic_test(const mgx_model* m, const mgx_assembly_logic_io* io, const mgx_assembly_env* e, int n_env,
                             void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  const int rc = check_common(m, nullptr, e);
-  if (rc) return rc;
-  if (io->max_contacts > m->L.max_ncon) return fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
+  if (io->max_contacts > m->L.max_ncon) return host_fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_assembly_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->as, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_assembly_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->as, *io, *e, n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->as, m->as, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

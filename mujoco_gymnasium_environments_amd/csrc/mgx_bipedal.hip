@@ -5,15 +5,13 @@
 // forward passes; constraint rows in per-env global scratch when the model's ~500 rows do not
 // fit LDS) -> victim interactions -> observation / reward / termination / stats, with
 // same-step autoreset (10 settle steps), all in one launch.
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
 MGX_PROF_SETTER(mgx_prof_set_buffer_bipedal)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 template <typename T, bool GB>
 __device__ __forceinline__ void bind(const DevModel<T>& m, Env<T>& e, char* smem, const mgx_state& s, int env) {
@@ -119,54 +117,40 @@ bool bipedal_env_ok(const mgx_bipedal_env* e) {
          e->ttfr && e->falls && e->collisions && e->prev_robot_pos;
 }
 
+constexpr Task<mgx_bipedal_env> kTask{"bipedal", "bipedal", &mgx_model::bipedal_ok, bipedal_env_ok, false};
 template <typename T>
-int configure_lds(const mgx_model* m) {
-  return mgx_set_lds(k_bipedal<T, 0, true>, m->L.bytes) | mgx_set_lds(k_bipedal<T, 1, true>, m->L.bytes) |
-         mgx_set_lds(k_bipedal<T, 0, false>, m->L.bytes) | mgx_set_lds(k_bipedal<T, 1, false>, m->L.bytes) |
-         mgx_set_lds(k_bipedal_logic<T>, m->L.bytes);
-}
-
-template <typename T, int MODE>
-void launch(const mgx_model* m, const DevModel<T>& M, const mgx_state* s, const mgx_bipedal_env* e, const float* action,
-            const T* draws, float* obs, double* reward, uint8_t* term, uint8_t* trunc, float* final_obs, int autoreset,
-            uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
-  if (m->L.gB)
-    hipLaunchKernelGGL((k_bipedal<T, MODE, true>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->bp, *s, *e, action,
-                       draws, obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-  else
-    hipLaunchKernelGGL((k_bipedal<T, MODE, false>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->bp, *s, *e, action,
-                       draws, obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-}
+constexpr auto kKernels = task_kernels(k_bipedal<T, 0, false>, k_bipedal<T, 0, true>, k_bipedal<T, 1, false>,
+                                       k_bipedal<T, 1, true>, k_bipedal_logic<T>);
 
 }  // namespace
 
 extern "C" {
 
 int mgx_bipedal_configure(mgx_model* m, const mgx_bipedal_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   bool f32 = m->precision == MGX_F32;
   int nq = f32 ? m->mf.nq : m->md.nq, nv = f32 ? m->mf.nv : m->md.nv, nu = f32 ? m->mf.nu : m->md.nu;
   int nb = f32 ? m->mf.nbody : m->md.nbody;
   if ((f32 ? m->mf.integrator : m->md.integrator) != 1)
-    return fail(MGX_E_UNSUPPORTED, "the bipedal kernels integrate with RK4 (rescue_env.py:148)");
+    return host_fail(MGX_E_UNSUPPORTED, "the bipedal kernels integrate with RK4 (rescue_env.py:148)");
   if ((f32 ? m->mf.solver : m->md.solver) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the bipedal kernels solve with PGS (rescue_env.py:146)");
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
-  if (ids->n_act != 26 || nu < 26) return fail(MGX_E_ARG, "bipedal needs 26 actuators written from the action");
-  if (ids->torso < 0 || ids->torso >= nb) return fail(MGX_E_ARG, "torso body id out of range");
+    return host_fail(MGX_E_UNSUPPORTED, "the bipedal kernels solve with PGS (rescue_env.py:146)");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->n_act != 26 || nu < 26) return host_fail(MGX_E_ARG, "bipedal needs 26 actuators written from the action");
+  if (ids->torso < 0 || ids->torso >= nb) return host_fail(MGX_E_ARG, "torso body id out of range");
   for (int i = 0; i < 5; i++) {
-    if (ids->victims[i] < 0 || ids->victims[i] >= nb) return fail(MGX_E_ARG, "victim body id out of range");
+    if (ids->victims[i] < 0 || ids->victims[i] >= nb) return host_fail(MGX_E_ARG, "victim body id out of range");
     if (ids->victim_x[i] < 0 || ids->victim_x[i] >= nq || ids->victim_y[i] < 0 || ids->victim_y[i] >= nq)
-      return fail(MGX_E_ARG, "victim qpos address out of range");
+      return host_fail(MGX_E_ARG, "victim qpos address out of range");
   }
   for (int i = 0; i < 26; i++)
     if (ids->obs_qposadr[i] < 0 || ids->obs_qposadr[i] >= nq || ids->obs_dofadr[i] < 0 || ids->obs_dofadr[i] >= nv)
-      return fail(MGX_E_ARG, "observed joint address out of range");
+      return host_fail(MGX_E_ARG, "observed joint address out of range");
   if (ids->root_x < 0 || ids->root_x >= nq || ids->root_y < 0 || ids->root_y >= nq || ids->root_z < 0 ||
       ids->root_z >= nq || ids->root_dof < 0 || ids->root_dof + 6 > nv)
-    return fail(MGX_E_ARG, "root joint address out of range");
-  int rc = f32 ? configure_lds<float>(m) : configure_lds<double>(m);
+    return host_fail(MGX_E_ARG, "root joint address out of range");
+  int rc = task_configure_lds(m, kKernels<float>, kKernels<double>);
   if (rc != MGX_OK) return rc;
   rc = bipedal_staged_configure(m);
   if (rc != MGX_OK) return rc;
@@ -188,66 +172,33 @@ int mgx_bipedal_configure(mgx_model* m, const mgx_bipedal_ids* ids) {
 int mgx_bipedal_step(const mgx_model* m, const mgx_state* s, const mgx_bipedal_env* e, const float* action, float* obs,
                      double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                      uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->bipedal_ok) return fail(MGX_E_ARG, "mgx_bipedal_configure not called");
-  if (!bipedal_env_ok(e)) return fail(MGX_E_ARG, "null bipedal env buffer");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace)  // the staged RK4 step (mgx_rk_staged.hip)
     return bipedal_step_staged(m, s, e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                                env_offset, n_env, mask, st);
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (m->precision == MGX_F32)
-    launch<float, 0>(m, m->mf, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 0>(m, m->md, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->bp, m->bp, 0, n_env, st, *e, action, RealPtr{nullptr},
+                     obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env, mask);
 }
 
 int mgx_bipedal_reset(const mgx_model* m, const mgx_state* s, const mgx_bipedal_env* e, const void* draws, float* obs,
                       uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->bipedal_ok) return fail(MGX_E_ARG, "mgx_bipedal_configure not called");
-  if (!bipedal_env_ok(e)) return fail(MGX_E_ARG, "null bipedal env buffer");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace)
     return bipedal_reset_staged(m, s, e, draws, obs, seed, env_offset, n_env, mask, st);
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (m->precision == MGX_F32)
-    launch<float, 1>(m, m->mf, s, e, nullptr, (const float*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 1>(m, m->md, s, e, nullptr, (const double*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->bp, m->bp, 1, n_env, st, *e, nullptr, RealPtr{draws},
+                     obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask);
 }
 
 int mgx_bipedal_logic_test(const mgx_model* m, const mgx_bipedal_logic_io* io, const mgx_bipedal_env* e, int n_env,
                            void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  if (!m->bipedal_ok) return fail(MGX_E_ARG, "mgx_bipedal_configure not called");
-  if (!bipedal_env_ok(e)) return fail(MGX_E_ARG, "null bipedal env buffer");
-  if (io->max_contacts > m->L.max_ncon) return fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
+  if (io->max_contacts > m->L.max_ncon) return host_fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_bipedal_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->bp, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_bipedal_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->bp, *io, *e, n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->bp, m->bp, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

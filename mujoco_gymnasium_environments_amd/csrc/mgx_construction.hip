@@ -8,15 +8,13 @@
 // reward / termination / observation, with same-step autoreset (mj_resetData + draws, no
 // forward pass), all in one launch. The rows B live in per-env global scratch.
 #define MGX_TEAM  // kernels with a Newton helper wave (lane_id, team_begin)
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
 MGX_PROF_SETTER(mgx_prof_set_buffer_construction)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 template <typename T>
 __device__ __forceinline__ void bind(const DevModel<T>& m, WEnv<T>& w, char* smem, const mgx_state& s, int env) {
@@ -230,29 +228,20 @@ __global__ void __launch_bounds__(64) k_wide_debug(DevModel<T> m, mgx_state s, i
 
 bool construction_env_ok(const mgx_construction_env* e) { return e->scal && e->ints && e->total_reward; }
 
+constexpr Task<mgx_construction_env> kTask{"construction", "construction", &mgx_model::construction_ok,
+                                            construction_env_ok, false};
+// rows in global scratch only (wide_supported): one kernel per MODE, named in both row placements
 template <typename T>
-int configure_lds(const mgx_model* m) {
-  return mgx_set_lds(k_construction<T, 0>, m->L.bytes) | mgx_set_lds(k_construction<T, 1>, m->L.bytes) |
-         mgx_set_lds(k_construction_logic<T>, m->L.bytes) | mgx_set_lds(k_wide_step<T>, m->L.bytes) |
-         mgx_set_lds(k_wide_debug<T>, m->L.bytes);
-}
-
-template <typename T, int MODE>
-void launch(const mgx_model* m, const DevModel<T>& M, const mgx_state* s, const mgx_construction_env* e,
-            const float* action, const T* draws, float* obs, double* reward, uint8_t* term, uint8_t* trunc,
-            float* final_obs, int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask,
-            hipStream_t st) {
-  hipLaunchKernelGGL((k_construction<T, MODE>), dim3(n_env), dim3(MODE == 0 ? kTeamThreads : 64), m->L.bytes, st, M, m->cn, *s, *e, action, draws,
-                     obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-}
+constexpr auto kKernels = task_kernels(k_construction<T, 0>, k_construction<T, 0>, k_construction<T, 1>,
+                                       k_construction<T, 1>, k_construction_logic<T>, kTeamThreads, 64);
 
 // a wide model's kernels: RK4 + Newton, rows in global scratch, nv <= 128
 int wide_supported(const mgx_model* m) {
   const bool f32 = m->precision == MGX_F32;
-  if (!m->wide) return fail(MGX_E_UNSUPPORTED, "the wide kernels are for models with 64 < nv <= 128");
+  if (!m->wide) return host_fail(MGX_E_UNSUPPORTED, "the wide kernels are for models with 64 < nv <= 128");
   if ((f32 ? m->mf.integrator : m->md.integrator) != 1 || (f32 ? m->mf.solver : m->md.solver) != 2)
-    return fail(MGX_E_UNSUPPORTED, "the wide kernels implement RK4 + Newton (construction_site.xml:10)");
-  if (!m->L.gB) return fail(MGX_E_UNSUPPORTED, "the wide kernels keep the constraint rows in global scratch");
+    return host_fail(MGX_E_UNSUPPORTED, "the wide kernels implement RK4 + Newton (construction_site.xml:10)");
+  if (!m->L.gB) return host_fail(MGX_E_UNSUPPORTED, "the wide kernels keep the constraint rows in global scratch");
   return MGX_OK;
 }
 
@@ -282,24 +271,26 @@ int wide_debug(const mgx_model* m, const mgx_state* s, int n_env, void* dbg, con
   return MGX_OK;
 }
 int wide_kernels_configure(const mgx_model* m) {
-  return m->precision == MGX_F32 ? configure_lds<float>(m) : configure_lds<double>(m);
+  return task_configure_lds(m, kKernels<float>, kKernels<double>) |
+         (m->precision == MGX_F32 ? mgx_set_lds(k_wide_step<float>, m->L.bytes) | mgx_set_lds(k_wide_debug<float>, m->L.bytes)
+                                  : mgx_set_lds(k_wide_step<double>, m->L.bytes) | mgx_set_lds(k_wide_debug<double>, m->L.bytes));
 }
 }  // namespace mgx
 
 extern "C" {
 
 int mgx_construction_configure(mgx_model* m, const mgx_construction_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
   int rc = wide_supported(m);
   if (rc) return rc;
   const bool f32 = m->precision == MGX_F32;
   const int nv = f32 ? m->mf.nv : m->md.nv, nu = f32 ? m->mf.nu : m->md.nu, nb = f32 ? m->mf.nbody : m->md.nbody;
   const int nq = f32 ? m->mf.nq : m->md.nq;
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
-  if (ids->n_act != nu || nu > 64) return fail(MGX_E_ARG, "n_act must equal nu (<= 64): ctrl[:] = action");
-  if (nq < 30 || nv < 30) return fail(MGX_E_ARG, "the observation reads qpos[:30] and qvel[:30]");
-  if (ids->humanoid < 0 || ids->humanoid >= nb) return fail(MGX_E_ARG, "humanoid body id out of range");
-  if (!(ids->action_limit > 0)) return fail(MGX_E_ARG, "action_limit must be > 0");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->n_act != nu || nu > 64) return host_fail(MGX_E_ARG, "n_act must equal nu (<= 64): ctrl[:] = action");
+  if (nq < 30 || nv < 30) return host_fail(MGX_E_ARG, "the observation reads qpos[:30] and qvel[:30]");
+  if (ids->humanoid < 0 || ids->humanoid >= nb) return host_fail(MGX_E_ARG, "humanoid body id out of range");
+  if (!(ids->action_limit > 0)) return host_fail(MGX_E_ARG, "action_limit must be > 0");
   ConstructionIds& o = m->cn;
   o.humanoid = ids->humanoid;
   o.n_act = ids->n_act;
@@ -312,61 +303,26 @@ int mgx_construction_configure(mgx_model* m, const mgx_construction_ids* ids) {
 int mgx_construction_step(const mgx_model* m, const mgx_state* s, const mgx_construction_env* e, const float* action,
                           float* obs, double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs,
                           int autoreset, uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->construction_ok) return fail(MGX_E_ARG, "mgx_construction_configure not called");
-  if (!construction_env_ok(e)) return fail(MGX_E_ARG, "null construction env buffer");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  const int rc = host_check_state(s);
-  if (rc) return rc;
-  if (!s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 0>(m, m->mf, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 0>(m, m->md, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->cn, m->cn, 0, n_env, (hipStream_t)stream, *e, action,
+                     RealPtr{nullptr}, obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env,
+                     mask);
 }
 
 int mgx_construction_reset(const mgx_model* m, const mgx_state* s, const mgx_construction_env* e, const void* draws,
                            float* obs, uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->construction_ok) return fail(MGX_E_ARG, "mgx_construction_configure not called");
-  if (!construction_env_ok(e)) return fail(MGX_E_ARG, "null construction env buffer");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  const int rc = host_check_state(s);
-  if (rc) return rc;
-  if (!s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 1>(m, m->mf, s, e, nullptr, (const float*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 1>(m, m->md, s, e, nullptr, (const double*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->cn, m->cn, 1, n_env, (hipStream_t)stream, *e, nullptr,
+                     RealPtr{draws}, obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask);
 }
 
 int mgx_construction_logic_test(const mgx_model* m, const mgx_construction_logic_io* io, const mgx_construction_env* e,
                                 int n_env, void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  if (!m->construction_ok) return fail(MGX_E_ARG, "mgx_construction_configure not called");
-  if (!construction_env_ok(e)) return fail(MGX_E_ARG, "null construction env buffer");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_construction_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->cn, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_construction_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->cn, *io, *e,
-                       n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->cn, m->cn, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

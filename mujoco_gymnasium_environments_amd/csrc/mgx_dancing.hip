@@ -4,15 +4,13 @@
 // (mgx_step.hip): a dancing env step is clip + rhythm + spotlight -> one RK4 mj_step (four
 // forward passes, rows in LDS) -> observation / reward / termination / stats / crowd / move
 // transition, with same-step autoreset (10 settle steps), all in one launch.
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
 MGX_PROF_SETTER(mgx_prof_set_buffer_dancing)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 template <typename T, bool GB>
 __device__ __forceinline__ void bind(const DevModel<T>& m, Env<T>& e, char* smem, const mgx_state& s, int env) {
@@ -123,46 +121,32 @@ bool dancing_env_ok(const mgx_dancing_env* e) {
   return e->scal && e->ints && e->hist && e->moves && e->durations && e->prev_jvel;
 }
 
+constexpr Task<mgx_dancing_env> kTask{"dancing", "dancing", &mgx_model::dancing_ok, dancing_env_ok, false};
 template <typename T>
-int configure_lds(const mgx_model* m) {
-  return mgx_set_lds(k_dancing<T, 0, true>, m->L.bytes) | mgx_set_lds(k_dancing<T, 1, true>, m->L.bytes) |
-         mgx_set_lds(k_dancing<T, 0, false>, m->L.bytes) | mgx_set_lds(k_dancing<T, 1, false>, m->L.bytes) |
-         mgx_set_lds(k_dancing_logic<T>, m->L.bytes);
-}
-
-template <typename T, int MODE>
-void launch(const mgx_model* m, const DevModel<T>& M, const mgx_state* s, const mgx_dancing_env* e, const float* action,
-            const T* draws, float* obs, double* reward, uint8_t* term, uint8_t* trunc, float* final_obs, int autoreset,
-            uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
-  if (m->L.gB)
-    hipLaunchKernelGGL((k_dancing<T, MODE, true>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->dn, *s, *e, action,
-                       draws, obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-  else
-    hipLaunchKernelGGL((k_dancing<T, MODE, false>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->dn, *s, *e, action,
-                       draws, obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-}
+constexpr auto kKernels = task_kernels(k_dancing<T, 0, false>, k_dancing<T, 0, true>, k_dancing<T, 1, false>,
+                                       k_dancing<T, 1, true>, k_dancing_logic<T>);
 
 }  // namespace
 
 extern "C" {
 
 int mgx_dancing_configure(mgx_model* m, const mgx_dancing_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   bool f32 = m->precision == MGX_F32;
   int nq = f32 ? m->mf.nq : m->md.nq, nv = f32 ? m->mf.nv : m->md.nv, nu = f32 ? m->mf.nu : m->md.nu;
   int nb = f32 ? m->mf.nbody : m->md.nbody;
   if ((f32 ? m->mf.integrator : m->md.integrator) != 1)
-    return fail(MGX_E_UNSUPPORTED, "the dancing kernels integrate with RK4 (dancing_env.py:179)");
+    return host_fail(MGX_E_UNSUPPORTED, "the dancing kernels integrate with RK4 (dancing_env.py:179)");
   if ((f32 ? m->mf.solver : m->md.solver) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the dancing kernels solve with PGS (dancing_env.py:177)");
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
-  if (ids->n_act != 29 || nu < 29) return fail(MGX_E_ARG, "dancing needs 29 actuators written from the action");
-  if (nv < 6 || nv > 64) return fail(MGX_E_ARG, "dancing observes qvel[6:] (6 < nv <= 64)");
-  if (ids->torso < 0 || ids->torso >= nb) return fail(MGX_E_ARG, "torso body id out of range");
-  if (ids->n_range < 0 || ids->n_range > 32) return fail(MGX_E_ARG, "n_range must be in [0, 32]");
+    return host_fail(MGX_E_UNSUPPORTED, "the dancing kernels solve with PGS (dancing_env.py:177)");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->n_act != 29 || nu < 29) return host_fail(MGX_E_ARG, "dancing needs 29 actuators written from the action");
+  if (nv < 6 || nv > 64) return host_fail(MGX_E_ARG, "dancing observes qvel[6:] (6 < nv <= 64)");
+  if (ids->torso < 0 || ids->torso >= nb) return host_fail(MGX_E_ARG, "torso body id out of range");
+  if (ids->n_range < 0 || ids->n_range > 32) return host_fail(MGX_E_ARG, "n_range must be in [0, 32]");
   (void)nq;
-  int rc = f32 ? configure_lds<float>(m) : configure_lds<double>(m);
+  int rc = task_configure_lds(m, kKernels<float>, kKernels<double>);
   if (rc != MGX_OK) return rc;
   DancingIds& o = m->dn;
   o.torso = ids->torso;
@@ -178,61 +162,27 @@ int mgx_dancing_configure(mgx_model* m, const mgx_dancing_ids* ids) {
 int mgx_dancing_step(const mgx_model* m, const mgx_state* s, const mgx_dancing_env* e, const float* action, float* obs,
                      double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                      uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->dancing_ok) return fail(MGX_E_ARG, "mgx_dancing_configure not called");
-  if (!dancing_env_ok(e)) return fail(MGX_E_ARG, "null dancing env buffer");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 0>(m, m->mf, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 0>(m, m->md, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->dn, m->dn, 0, n_env, (hipStream_t)stream, *e, action,
+                     RealPtr{nullptr}, obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env,
+                     mask);
 }
 
 int mgx_dancing_reset(const mgx_model* m, const mgx_state* s, const mgx_dancing_env* e, const void* draws, float* obs,
                       uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->dancing_ok) return fail(MGX_E_ARG, "mgx_dancing_configure not called");
-  if (!dancing_env_ok(e)) return fail(MGX_E_ARG, "null dancing env buffer");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 1>(m, m->mf, s, e, nullptr, (const float*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 1>(m, m->md, s, e, nullptr, (const double*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->dn, m->dn, 1, n_env, (hipStream_t)stream, *e, nullptr,
+                     RealPtr{draws}, obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask);
 }
 
 int mgx_dancing_logic_test(const mgx_model* m, const mgx_dancing_logic_io* io, const mgx_dancing_env* e, int n_env,
                            void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  if (!m->dancing_ok) return fail(MGX_E_ARG, "mgx_dancing_configure not called");
-  if (!dancing_env_ok(e)) return fail(MGX_E_ARG, "null dancing env buffer");
-  if (io->max_contacts > m->L.max_ncon) return fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
+  if (io->max_contacts > m->L.max_ncon) return host_fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_dancing_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->dn, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_dancing_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->dn, *io, *e, n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->dn, m->dn, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

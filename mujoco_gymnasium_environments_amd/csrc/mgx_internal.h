@@ -1,6 +1,7 @@
 // mgx_internal.h — host-side definitions shared by the translation units of libmgx.so
 // (mgx_api.hip: model, physics and soccer; mgx_step.hip: generic step; mgx_parkour.hip:
-// quadruped_parkour; mgx_bipedal.hip: bipedal_rescue; mgx_dancing.hip: humanoid_dancing).
+// quadruped_parkour; mgx_bipedal.hip: bipedal_rescue; mgx_dancing.hip: humanoid_dancing;
+// mgx_task_host.h: the checks and the kernel dispatch the task entries share).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,6 +115,8 @@ int wide_kernels_configure(const mgx_model* m);
 // records the message returned by mgx_last_error() and returns `code`
 int host_fail(int code, const std::string& msg);
 int host_check_state(const mgx_state* s);
+// a model whose constraint rows live in per-env global scratch (Layout.gB) needs mgx_state.scratch
+int host_check_scratch(const mgx_model* m, const mgx_state* s);
 // dynamic-LDS attributes of the generic step kernels (mgx_step.hip)
 int step_kernels_configure(const mgx_model* m);
 // the staged solver S2 (mgx_pgs.hip)

@@ -5,15 +5,13 @@
 // (Euler, Newton: the Hessian and its Cholesky factor in the env's LDS) -> observation / reward /
 // termination / statistics, with same-step autoreset (mj_forward, no settle steps), all in one
 // launch.
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
 MGX_PROF_SETTER(mgx_prof_set_buffer_martial)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 template <typename T>
 __device__ __forceinline__ void martial_reset_philox(const DevModel<T>& m, Env<T>& e, const MartialIds& ids, mgx_state s,
@@ -112,51 +110,38 @@ __global__ void __launch_bounds__(64) k_martial_logic(DevModel<T> m, MartialIds 
 
 bool martial_env_ok(const mgx_martial_env* e) { return e->scal && e->ints; }
 
-template <typename T, int MODE>
-void launch(const mgx_model* m, const DevModel<T>& M, const mgx_state* s, const mgx_martial_env* e, const float* action,
-            const T* draws, float* obs, double* reward, uint8_t* term, uint8_t* trunc, float* final_obs, int autoreset,
-            uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
-  if (m->L.gB)
-    hipLaunchKernelGGL((k_martial<T, MODE, true>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->ma, *s, *e, action, draws,
-                       obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-  else
-    hipLaunchKernelGGL((k_martial<T, MODE, false>), dim3(n_env), dim3(64), m->L.bytes, st, M, m->ma, *s, *e, action, draws,
-                       obs, reward, term, trunc, final_obs, autoreset, seed, env_offset, n_env, mask);
-}
+constexpr Task<mgx_martial_env> kTask{"martial", "martial-arts", &mgx_model::martial_ok, martial_env_ok, false};
+template <typename T>
+constexpr auto kKernels = task_kernels(k_martial<T, 0, false>, k_martial<T, 0, true>, k_martial<T, 1, false>,
+                                       k_martial<T, 1, true>, k_martial_logic<T>);
 
 }  // namespace
 
 extern "C" {
 
 int mgx_martial_configure(mgx_model* m, const mgx_martial_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   const bool f32 = m->precision == MGX_F32;
   const int nq = f32 ? m->mf.nq : m->md.nq, nv = f32 ? m->mf.nv : m->md.nv, nu = f32 ? m->mf.nu : m->md.nu;
   const int nb = f32 ? m->mf.nbody : m->md.nbody;
   if ((f32 ? m->mf.integrator : m->md.integrator) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the martial-arts kernels need an Euler model");
+    return host_fail(MGX_E_UNSUPPORTED, "the martial-arts kernels need an Euler model");
   if ((f32 ? m->mf.solver : m->md.solver) != 2)
-    return fail(MGX_E_UNSUPPORTED, "the martial-arts kernels solve with Newton (martial_arts_scene.xml:163)");
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
-  if (ids->n_act != nu || nu > 32) return fail(MGX_E_ARG, "n_act must equal nu (<= 32): ctrl[:] = action * ctrlrange");
-  if (29 + (nq - 7) + (nv - 6) != MGX_MARTIAL_OBS) return fail(MGX_E_ARG, "the observation needs nq - 7 + nv - 6 == 84");
+    return host_fail(MGX_E_UNSUPPORTED, "the martial-arts kernels solve with Newton (martial_arts_scene.xml:163)");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->n_act != nu || nu > 32) return host_fail(MGX_E_ARG, "n_act must equal nu (<= 32): ctrl[:] = action * ctrlrange");
+  if (29 + (nq - 7) + (nv - 6) != MGX_MARTIAL_OBS) return host_fail(MGX_E_ARG, "the observation needs nq - 7 + nv - 6 == 84");
   const int b[7] = {ids->torso, ids->right_hand, ids->left_hand, ids->right_foot, ids->left_foot, ids->dummy1, ids->dummy2};
   for (int k = 0; k < 7; k++)
-    if (b[k] < 0 || b[k] >= nb) return fail(MGX_E_ARG, "body id out of range");
+    if (b[k] < 0 || b[k] >= nb) return host_fail(MGX_E_ARG, "body id out of range");
   MartialIds& o = m->ma;
   o.torso = ids->torso; o.right_hand = ids->right_hand; o.left_hand = ids->left_hand;
   o.right_foot = ids->right_foot; o.left_foot = ids->left_foot; o.dummy1 = ids->dummy1; o.dummy2 = ids->dummy2;
   o.n_act = ids->n_act;
   o.max_episode_steps = ids->max_episode_steps;
   for (int k = 0; k < 32; k++) o.ctrl_scale[k] = ids->ctrl_scale[k];
-  const int rc =
-      f32 ? (mgx_set_lds(k_martial<float, 0, false>, m->L.bytes) | mgx_set_lds(k_martial<float, 1, false>, m->L.bytes) |
-             mgx_set_lds(k_martial<float, 0, true>, m->L.bytes) | mgx_set_lds(k_martial<float, 1, true>, m->L.bytes) |
-             mgx_set_lds(k_martial_logic<float>, m->L.bytes))
-          : (mgx_set_lds(k_martial<double, 0, false>, m->L.bytes) | mgx_set_lds(k_martial<double, 1, false>, m->L.bytes) |
-             mgx_set_lds(k_martial<double, 0, true>, m->L.bytes) | mgx_set_lds(k_martial<double, 1, true>, m->L.bytes) |
-             mgx_set_lds(k_martial_logic<double>, m->L.bytes));
+  const int rc = task_configure_lds(m, kKernels<float>, kKernels<double>);
   if (rc != MGX_OK) return rc;
   m->martial_ok = true;
   return MGX_OK;
@@ -165,60 +150,26 @@ int mgx_martial_configure(mgx_model* m, const mgx_martial_ids* ids) {
 int mgx_martial_step(const mgx_model* m, const mgx_state* s, const mgx_martial_env* e, const float* action, float* obs,
                      double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                      uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->martial_ok) return fail(MGX_E_ARG, "mgx_martial_configure not called");
-  if (!martial_env_ok(e)) return fail(MGX_E_ARG, "null martial-arts env buffer");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  const int rc = host_check_state(s);
-  if (rc) return rc;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 0>(m, m->mf, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 0>(m, m->md, s, e, action, nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->ma, m->ma, 0, n_env, (hipStream_t)stream, *e, action,
+                     RealPtr{nullptr}, obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env,
+                     mask);
 }
 
 int mgx_martial_reset(const mgx_model* m, const mgx_state* s, const mgx_martial_env* e, const void* draws, float* obs,
                       uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->martial_ok) return fail(MGX_E_ARG, "mgx_martial_configure not called");
-  if (!martial_env_ok(e)) return fail(MGX_E_ARG, "null martial-arts env buffer");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  const int rc = host_check_state(s);
-  if (rc) return rc;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    launch<float, 1>(m, m->mf, s, e, nullptr, (const float*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                     env_offset, n_env, mask, st);
-  else
-    launch<double, 1>(m, m->md, s, e, nullptr, (const double*)draws, obs, nullptr, nullptr, nullptr, nullptr, 0, seed,
-                      env_offset, n_env, mask, st);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->ma, m->ma, 1, n_env, (hipStream_t)stream, *e, nullptr,
+                     RealPtr{draws}, obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask);
 }
 
 int mgx_martial_logic_test(const mgx_model* m, const mgx_martial_logic_io* io, const mgx_martial_env* e, int n_env,
                            void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  if (!m->martial_ok) return fail(MGX_E_ARG, "mgx_martial_configure not called");
-  if (!martial_env_ok(e)) return fail(MGX_E_ARG, "null martial-arts env buffer");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_martial_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->ma, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_martial_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->ma, *io, *e, n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->ma, m->ma, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

@@ -4,15 +4,13 @@
 // LDS layout as the monolithic soccer step (mgx_physics.h): a parkour env step is
 // clip -> 10 x mj_step (dt 1 ms, PGS, Euler; plane contacts) -> obstacle motors ->
 // observation / reward / termination, with same-step autoreset, all in one launch.
-#include "mgx_internal.h"
+#include "mgx_task_host.h"
 
 using namespace mgx;
 
 MGX_PROF_SETTER(mgx_prof_set_buffer_parkour)
 
 namespace {
-
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
 
 // Philox-drawn reset of `env` for its current episode counter (the counter then advances);
 // writes the state back to HBM.
@@ -134,47 +132,37 @@ bool parkour_env_ok(const mgx_parkour_env* e) {
          e->stuck && e->step;
 }
 
-}  // namespace
-
+constexpr Task<mgx_parkour_env> kTask{"parkour", "parkour", &mgx_model::parkour_ok, parkour_env_ok, false};
 // rows in LDS or, with MGX_ROWS_IN_SCRATCH / an oversize model, in per-env global scratch
-#define MGX_PK_LAUNCH(T, MODE, ...)                                  \
-  do {                                                               \
-    if (m->L.gB) hipLaunchKernelGGL((k_parkour<T, MODE, true>), __VA_ARGS__);  \
-    else hipLaunchKernelGGL((k_parkour<T, MODE, false>), __VA_ARGS__);        \
-  } while (0)
+template <typename T>
+constexpr auto kKernels = task_kernels(k_parkour<T, 0, false>, k_parkour<T, 0, true>, k_parkour<T, 1, false>,
+                                       k_parkour<T, 1, true>, k_parkour_logic<T>);
+
+}  // namespace
 
 extern "C" {
 
 int mgx_parkour_configure(mgx_model* m, const mgx_parkour_ids* ids) {
-  if (!m || !ids) return fail(MGX_E_ARG, "null argument");
-  if (m->wide) return fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
+  if (!m || !ids) return host_fail(MGX_E_ARG, "null argument");
+  if (m->wide) return host_fail(MGX_E_UNSUPPORTED, MGX_WIDE_MSG);
   int nq = m->precision == MGX_F32 ? m->mf.nq : m->md.nq;
   int nu = m->precision == MGX_F32 ? m->mf.nu : m->md.nu;
   int nb = m->precision == MGX_F32 ? m->mf.nbody : m->md.nbody;
-  if (ids->max_episode_steps <= 0) return fail(MGX_E_ARG, "max_episode_steps must be > 0");
+  if (ids->max_episode_steps <= 0) return host_fail(MGX_E_ARG, "max_episode_steps must be > 0");
   if ((m->precision == MGX_F32 ? m->mf.integrator : m->md.integrator) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the parkour kernels need an Euler model whose rows fit LDS");
+    return host_fail(MGX_E_UNSUPPORTED, "the parkour kernels need an Euler model whose rows fit LDS");
   if ((m->precision == MGX_F32 ? m->mf.solver : m->md.solver) != 0)
-    return fail(MGX_E_UNSUPPORTED, "the parkour kernels solve with PGS (quadruped.xml:4)");
-  if (ids->n_leg != 16 || nu < 16 || nq < 7) return fail(MGX_E_ARG, "parkour needs 16 leg actuators and a free root");
-  if (ids->torso < 0 || ids->torso >= nb) return fail(MGX_E_ARG, "torso body id out of range");
+    return host_fail(MGX_E_UNSUPPORTED, "the parkour kernels solve with PGS (quadruped.xml:4)");
+  if (ids->n_leg != 16 || nu < 16 || nq < 7) return host_fail(MGX_E_ARG, "parkour needs 16 leg actuators and a free root");
+  if (ids->torso < 0 || ids->torso >= nb) return host_fail(MGX_E_ARG, "torso body id out of range");
   for (int i = 0; i < 4; i++)
-    if (ids->feet[i] < 0 || ids->feet[i] >= nb) return fail(MGX_E_ARG, "foot body id out of range");
+    if (ids->feet[i] < 0 || ids->feet[i] >= nb) return host_fail(MGX_E_ARG, "foot body id out of range");
   if (ids->platform_qpos < 0 || ids->platform_qpos >= nq || ids->pendulum_qpos < 0 || ids->pendulum_qpos >= nq)
-    return fail(MGX_E_ARG, "obstacle qpos index out of range");
-  if (ids->platform_act >= nu || ids->pendulum_act >= nu) return fail(MGX_E_ARG, "obstacle actuator id out of range");
-  int rc;
-  if (m->precision == MGX_F32) {
-    fill_parkour_ids(m->pkf, ids);
-    rc = mgx_set_lds(k_parkour<float, 0, false>, m->L.bytes) | mgx_set_lds(k_parkour<float, 1, false>, m->L.bytes) |
-         mgx_set_lds(k_parkour<float, 0, true>, m->L.bytes) | mgx_set_lds(k_parkour<float, 1, true>, m->L.bytes) |
-         mgx_set_lds(k_parkour_logic<float>, m->L.bytes);
-  } else {
-    fill_parkour_ids(m->pkd, ids);
-    rc = mgx_set_lds(k_parkour<double, 0, false>, m->L.bytes) | mgx_set_lds(k_parkour<double, 1, false>, m->L.bytes) |
-         mgx_set_lds(k_parkour<double, 0, true>, m->L.bytes) | mgx_set_lds(k_parkour<double, 1, true>, m->L.bytes) |
-         mgx_set_lds(k_parkour_logic<double>, m->L.bytes);
-  }
+    return host_fail(MGX_E_ARG, "obstacle qpos index out of range");
+  if (ids->platform_act >= nu || ids->pendulum_act >= nu) return host_fail(MGX_E_ARG, "obstacle actuator id out of range");
+  if (m->precision == MGX_F32) fill_parkour_ids(m->pkf, ids);
+  else fill_parkour_ids(m->pkd, ids);
+  int rc = task_configure_lds(m, kKernels<float>, kKernels<double>);
   if (rc != MGX_OK) return rc;
   rc = parkour_staged_configure(m);
   if (rc != MGX_OK) return rc;
@@ -185,54 +173,24 @@ int mgx_parkour_configure(mgx_model* m, const mgx_parkour_ids* ids) {
 int mgx_parkour_step(const mgx_model* m, const mgx_state* s, const mgx_parkour_env* e, const float* action, float* obs,
                      double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                      uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !action || !obs || !reward || !terminated || !truncated) return fail(MGX_E_ARG, "null argument");
-  if (e->action_f64 != 0 && e->action_f64 != 1) return fail(MGX_E_ARG, "action_f64 must be 0 (float32) or 1 (float64)");
-  if (!m->parkour_ok) return fail(MGX_E_ARG, "mgx_parkour_configure not called");
-  if (!parkour_env_ok(e)) return fail(MGX_E_ARG, "null parkour env buffer");
-  if (autoreset && !e->episode) return fail(MGX_E_ARG, "autoreset needs the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_step(kTask, m, s, e, action && obs && reward && terminated && truncated, autoreset, n_env))
+    return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace)  // the staged step (mgx_pk_staged.hip)
     return parkour_step_staged(m, s, e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                                env_offset, n_env, mask, st);
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (m->precision == MGX_F32)
-    MGX_PK_LAUNCH(float, 0, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->pkf, *s, *e, action,
-                       (const float*)nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                       env_offset, n_env, mask);
-  else
-    MGX_PK_LAUNCH(double, 0, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->pkd, *s, *e, action,
-                       (const double*)nullptr, obs, reward, terminated, truncated, final_obs, autoreset, seed,
-                       env_offset, n_env, mask);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->pkf, m->pkd, 0, n_env, st, *e, action, RealPtr{nullptr},
+                     obs, reward, terminated, truncated, final_obs, autoreset, seed, env_offset, n_env, mask);
 }
 
 int mgx_parkour_reset(const mgx_model* m, const mgx_state* s, const mgx_parkour_env* e, const void* draws, float* obs,
                       uint64_t seed, int env_offset, int n_env, const uint8_t* mask, void* stream) {
-  if (!m || !e || !obs) return fail(MGX_E_ARG, "null argument");
-  if (!m->parkour_ok) return fail(MGX_E_ARG, "mgx_parkour_configure not called");
-  if (!parkour_env_ok(e)) return fail(MGX_E_ARG, "null parkour env buffer");
-  if (!draws && !e->episode) return fail(MGX_E_ARG, "device draws need the episode counter buffer");
-  int rc = host_check_state(s);
-  if (rc) return rc;
-  if (n_env <= 0) return MGX_OK;
+  if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace)  // every reset of a staged batch settles through the staged stages
     return parkour_reset_staged(m, s, e, draws, obs, seed, env_offset, n_env, mask, st);
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
-  if (m->precision == MGX_F32)
-    MGX_PK_LAUNCH(float, 1, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->pkf, *s, *e,
-                       (const float*)nullptr, (const float*)draws, obs, (double*)nullptr, (uint8_t*)nullptr,
-                       (uint8_t*)nullptr, (float*)nullptr, 0, seed, env_offset, n_env, mask);
-  else
-    MGX_PK_LAUNCH(double, 1, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->pkd, *s, *e,
-                       (const float*)nullptr, (const double*)draws, obs, (double*)nullptr, (uint8_t*)nullptr,
-                       (uint8_t*)nullptr, (float*)nullptr, 0, seed, env_offset, n_env, mask);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch(m, s, kKernels<float>, kKernels<double>, m->pkf, m->pkd, 1, n_env, st, *e, nullptr, RealPtr{draws},
+                     obs, nullptr, nullptr, nullptr, nullptr, 0, seed, env_offset, n_env, mask);
 }
 
 int64_t mgx_parkour_workspace_bytes(const mgx_model* m, int n_env, int banks) {
@@ -244,18 +202,11 @@ int mgx_parkour_workspace_init(const mgx_model* m, void* workspace, uint64_t byt
 
 int mgx_parkour_logic_test(const mgx_model* m, const mgx_parkour_logic_io* io, const mgx_parkour_env* e, int n_env,
                            void* stream) {
-  if (!m || !io || !e) return fail(MGX_E_ARG, "null argument");
-  if (!m->parkour_ok) return fail(MGX_E_ARG, "mgx_parkour_configure not called");
-  if (!parkour_env_ok(e)) return fail(MGX_E_ARG, "null parkour env buffer");
-  if (io->max_contacts > m->L.max_ncon) return fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
+  if (int rc = task_check(kTask, m, e, io)) return rc;
+  if (io->max_contacts > m->L.max_ncon) return host_fail(MGX_E_CAPACITY, "max_contacts exceeds the contact capacity");
   if (n_env <= 0) return MGX_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_parkour_logic<float>, dim3(n_env), dim3(64), m->L.bytes, st, m->mf, m->pkf, *io, *e, n_env);
-  else
-    hipLaunchKernelGGL(k_parkour_logic<double>, dim3(n_env), dim3(64), m->L.bytes, st, m->md, m->pkd, *io, *e, n_env);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return task_launch_logic(m, kKernels<float>, kKernels<double>, m->pkf, m->pkd, n_env, (hipStream_t)stream, *io, *e,
+                           n_env);
 }
 
 }  // extern "C"

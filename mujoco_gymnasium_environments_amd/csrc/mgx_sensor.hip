@@ -573,8 +573,8 @@ int mgx_forward(const mgx_model* m, const mgx_state* s, const mgx_forward_out* o
   int rc = host_check_state(s);
   if (rc) return rc;
   if (n_env == 0) return MGX_OK;
-  if (m->L.gB && !s->scratch)
-    return host_fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
+  rc = host_check_scratch(m, s);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (m->precision == MGX_F32) {
     if (m->L.gB) launch_forward_v<float, true>(m, m->mf, s, fwd_buf<float>(out), n_env, env_mask, st);

@@ -191,7 +191,8 @@ int mgx_step(const mgx_model* m, const mgx_state* s, mgx_frames* frames, int n_e
   if (n_env == 0 || nsub == 0) return MGX_OK;
   mgx_frames fr{};
   if (frames) fr = *frames;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
+  rc = host_check_scratch(m, s);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (m->wide) return wide_step(m, s, fr, n_env, nsub, mask, st);
   if (m->precision == MGX_F32) launch_step<float>(m, m->mf, s, fr, n_env, nsub, mask, st);
@@ -230,7 +231,8 @@ int mgx_debug_forward(const mgx_model* m, const mgx_state* s, int n_env, void* d
   int rc = check_state(s);
   if (rc) return rc;
   if (n_env <= 0) return MGX_OK;
-  if (m->L.gB && !s->scratch) return fail(MGX_E_ARG, "this model needs mgx_state.scratch (scratch_bytes_per_env)");
+  rc = host_check_scratch(m, s);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (m->wide) {
     DbgOff o = m->precision == MGX_F32

@@ -23,23 +23,16 @@ and every substep ends in a bad-state reset, so ``precision="f32"`` is refused.
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets",
                      "robotic_arm_assembly.xml")
@@ -145,69 +138,35 @@ class AssemblyTables:
         return s
 
 
-class AssemblyVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU."""
+class AssemblyVectorEnv(TaskVectorEnv):
+    """``num_envs`` robotic_arm_assembly envs stepping in lockstep on one GPU, 10 mj_steps per env
+    step. ``step(actions)`` takes [N, 9]: 7 joint commands, gripper opening (mm), grip force (unused
+    by the reference, :252-265). reset() is deterministic: no seed, env offset or draws."""
 
     metadata = {'render_modes': [], 'render_fps': 50}
+    TASK, ENV_STRUCT, OBS_DIM, SEEDED = "assembly", cabi.MgxAssemblyEnv, OBS_DIM, False
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64",
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True):
         if precision != "f64":
             raise ValueError("robotic_arm_assembly runs in fp64 only: its degenerate base contact (R = 1e-15, "
                              "~1e17 forces) breaks the fp32 Newton factorisation (module docstring)")
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = assembly_model()
-        self.tables = AssemblyTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
+        model = assembly_model()
+        self._setup(num_envs, device, precision, model, AssemblyTables(model, max_episode_steps), autoreset)
         dev, N = self.device, num_envs
         self.ints = torch.zeros(N, 16, dtype=torch.int32, device=dev)
         self.ints[:, 1] = -1
         self.cumulative = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.rollout = torch.zeros(N, 4, dtype=torch.float64, device=dev)
         self.reset_qpos = torch.as_tensor(self.tables.reset_qpos, dtype=torch.float64, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxAssemblyEnv(*[t.data_ptr() for t in (self.ints, self.cumulative, self.episode,
-                                                                   self.rollout, self.reset_qpos)])
-        ids = self.tables.ids_struct()
-        check(lib().mgx_assembly_configure(self.native.handle, C.byref(ids)), "mgx_assembly_configure")
+        self._bind(self.ints, self.cumulative, self.episode, self.rollout, self.reset_qpos)
         self.action_space = Box(low=np.array(ACTION_LOW, np.float32), high=np.array(ACTION_HIGH, np.float32),
                                 dtype=np.float32)
 
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
+    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None, stream=None):
         """reset() for all (or masked) envs: deterministic (the seed only reseeds gymnasium's
         np_random, which the reference never draws from)."""
-        if seed is not None:
-            self.episode.zero_()
-        check(lib().mgx_assembly_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                       _ptr(self.obs), self.num_envs, _ptr(env_mask), stream_handle(stream)),
-              "mgx_assembly_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step (10 mj_steps) for every env. ``actions`` float32 [N, 9]: 7 joint
-        commands, gripper opening (mm), grip force (unused by the reference, :252-265)."""
-        # float32, or float64: the reference's np.clip keeps a float64 policy's dtype, so ctrl and the
-        # action terms of the reward follow in float64 (include/mgx.h action_f64)
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        assert actions.shape == (self.num_envs, N_ACT), actions.shape
-        check(lib().mgx_assembly_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                      _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                      _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                      1 if self.autoreset else 0, self.num_envs, None, stream_handle(stream)),
-              "mgx_assembly_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
+        return super().reset(seed=seed, env_mask=env_mask, stream=stream)
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (:474-484)."""
@@ -223,11 +182,8 @@ class AssemblyVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tra
             'bad_state_resets': self.batch.warning,
         }
 
-    def close(self):
-        pass
 
-
-class RoboticArmAssemblyEnv(EnvBase):
+class RoboticArmAssemblyEnv(TaskEnv):
     """Drop-in for robotic_arm_assembly_env.assembly_env.RoboticArmAssemblyEnv on libmgx.
     Actions are taken as float32 (np.clip against the float32 action_space bounds keeps float32
     actions float32, so a[7] / 1000 is a float32 division, as in the reference for float32
@@ -260,15 +216,10 @@ class RoboticArmAssemblyEnv(EnvBase):
         self.reset()
 
     def reset(self, seed: Optional[int] = None, options: Optional[Dict] = None):
-        obs, _ = self._vec.reset(seed=seed)
-        torch.cuda.synchronize(self._vec.device)
-        return obs[0].cpu().numpy().copy(), self._get_info()
+        return self._reset_vec(seed), self._get_info()
 
     def step(self, action: np.ndarray):
-        a = torch.from_numpy(policy_action(action).reshape(1, -1)).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
-        return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), self._get_info()
+        return (*self._step_vec(action), self._get_info())
 
     # reference attribute names, read back from the device state
     @property
@@ -310,6 +261,3 @@ class RoboticArmAssemblyEnv(EnvBase):
         if self.render_mode == "rgb_array":
             return np.zeros((480, 640, 3), dtype=np.uint8)  # :494-497
         return None
-
-    def close(self):
-        self.viewer = None

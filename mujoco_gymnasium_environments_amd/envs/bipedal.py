@@ -19,24 +19,16 @@ so its rows live in global scratch (Layout.gB) rather than LDS.
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import NativeError, check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "bipedal_rescue.xml")
 # MuJoCo keeps every contact (no arena limit at these sizes). Measured at bench conditions (U(-100,
@@ -112,10 +104,14 @@ class BipedalTables:
         return np.array(d)
 
 
-class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU."""
+class BipedalVectorEnv(TaskVectorEnv):
+    """``num_envs`` bipedal_rescue envs stepping in lockstep on one GPU, one RK4 mj_step per env
+    step. ``step(actions)`` takes [N, 26] float32, or float64: a float64 action is clipped and
+    applied in float64 and its energy terms follow in float64 (rescue_env.py:420-429, :650);
+    ``reset(draws=)`` takes [N, 12]."""
 
     metadata = {'render_modes': [], 'render_fps': 50}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "bipedal", cabi.MgxBipedalEnv, OBS_DIM, 12
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0,
@@ -131,15 +127,9 @@ class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
         (``staged=False``) keeps its rows in per-env scratch sized for 512 rows and drops rows past
         that in MuJoCo's order, counted in ``batch.overflow`` — the two paths compute the same
         physics on every env step under 512 rows (tests/test_gpu_bipedal.py)."""
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = bipedal_model()
-        self.tables = BipedalTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = bipedal_model()
+        self._setup(num_envs, device, precision, model, BipedalTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dev, N = self.device, num_envs
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
@@ -164,64 +154,14 @@ class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
         self.falls = torch.zeros(N, **i32)
         self.collisions = torch.zeros(N, **i32)
         self.prev_robot_pos = torch.zeros(N, 3, **f64)
-        self.episode = torch.zeros(N, **i32)
         self.rollout = torch.zeros(N, 4, dtype=self.batch.dtype, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, **f64)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxBipedalEnv(*[t.data_ptr() for t in (
-            self.step_count, self.energy, self.energy_used, self.rescued, self.carried, self.carrying, self.closest,
-            self.prev_rescued, self.prev_carried, self.prev_sz, self.fall_timer, self.victims_rescued, self.distance,
-            self.ttfr, self.falls, self.collisions, self.prev_robot_pos, self.episode, self.rollout)])
-        self._env.energy_kind = self.energy_kind.data_ptr()
-        ids = self.tables.ids_struct()
-        check(lib().mgx_bipedal_configure(self.native.handle, C.byref(ids)), "mgx_bipedal_configure")
-        self.staged = staged
-        self.workspace = None
+        self._bind(self.step_count, self.energy, self.energy_used, self.rescued, self.carried, self.carrying,
+                   self.closest, self.prev_rescued, self.prev_carried, self.prev_sz, self.fall_timer,
+                   self.victims_rescued, self.distance, self.ttfr, self.falls, self.collisions, self.prev_robot_pos,
+                   self.episode, self.rollout, energy_kind=self.energy_kind)
         if staged:
-            nb = int(lib().mgx_bipedal_workspace_bytes(self.native.handle, N, banks))
-            if nb <= 0:
-                raise NativeError(f"mgx_bipedal_workspace_bytes: {lib().mgx_last_error().decode()}")
-            self.workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-            check(lib().mgx_bipedal_workspace_init(self.native.handle, _ptr(self.workspace), nb, N, banks, None),
-                  "mgx_bipedal_workspace_init")
-            self._env.workspace = self.workspace.data_ptr()
-            self._env.workspace_bytes = nb
-            self._env.banks = banks
+            self._stage(banks)
         self.action_space = Box(low=-ACTION_LIMIT, high=ACTION_LIMIT, shape=(N_ACT,), dtype=np.float32)
-
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,12] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 12), dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_bipedal_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                      _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs, _ptr(env_mask),
-                                      stream_handle(stream)), "mgx_bipedal_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step (one RK4 mj_step) for every env. ``actions`` [N, 26] float32, or float64: a
-        float64 action is clipped and applied in float64 and its energy terms follow in float64, as
-        the reference's np.clip keeps a float64 policy's dtype (rescue_env.py:420-429, :650)."""
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        assert actions.shape == (self.num_envs, N_ACT), actions.shape
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        check(lib().mgx_bipedal_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                     _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                     _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                     1 if self.autoreset else 0, self.seed_value, self.env_offset, self.num_envs,
-                                     None, stream_handle(stream)), "mgx_bipedal_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (rescue_env.py:447-456); views only, so
@@ -242,9 +182,6 @@ class BipedalVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
             'bad_state_resets': self.batch.warning,
         }
 
-    def close(self):
-        pass
-
 
 def _popcount5(x: torch.Tensor) -> torch.Tensor:
     c = torch.zeros_like(x)
@@ -253,7 +190,7 @@ def _popcount5(x: torch.Tensor) -> torch.Tensor:
     return c
 
 
-class BipedalRescueEnv(EnvBase):
+class BipedalRescueEnv(TaskEnv):
     """Drop-in for bipedal_rescue_env.rescue_env.BipedalRescueEnv, simulated by libmgx."""
 
     metadata = {'render_modes': ['human', 'rgb_array', 'depth_array'], 'render_fps': 50}
@@ -287,29 +224,16 @@ class BipedalRescueEnv(EnvBase):
         self.current_step = 0
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.current_step = 0
         info = self._info()
-        return obs[0].cpu().numpy().copy(), {k: info[k] for k in
-                                              ('episode_stats', 'robot_position', 'victims_remaining',
-                                               'energy_remaining')}
+        return obs, {k: info[k] for k in ('episode_stats', 'robot_position', 'victims_remaining', 'energy_remaining')}
 
     def step(self, action: np.ndarray):
-        a = torch.from_numpy(policy_action(action).reshape(1, -1)).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        out = self._step_vec(action)
         self.current_step = int(self._vec.step_count[0])
-        info = self._info()
-        return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), info
+        return (*out, self._info())
 
     def _info(self) -> Dict[str, Any]:
         v = self._vec
@@ -330,12 +254,6 @@ class BipedalRescueEnv(EnvBase):
         """numpy type of current_energy / energy_used: a Python float after reset, np.float32 after
         float32 actions, np.float64 once a float64 action's cost was subtracted"""
         return {0: float, 1: np.float64, 2: np.float32}[int(self._vec.energy_kind[0])]
-
-    def render(self):
-        return None  # rescue_env.py:779-783 (viewer sync only)
-
-    def close(self):
-        self.viewer = None
 
 
 def register_envs() -> bool:

@@ -18,24 +18,16 @@ pass (C4).
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box, policy_action
+from .base import TaskEnv, TaskVectorEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets",
                      "humanoid_construction.xml")
@@ -87,22 +79,18 @@ class ConstructionTables:
         return np.array([task, rng.uniform(0, 5), rng.uniform(0, 0.5), rng.uniform(15, 35)], dtype=np.float64)
 
 
-class ConstructionVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` humanoid_construction envs stepping in lockstep on one GPU."""
+class ConstructionVectorEnv(TaskVectorEnv):
+    """``num_envs`` humanoid_construction envs stepping in lockstep on one GPU. ``step(actions)``
+    takes [N, nu] float32 or float64 (clipped to +-200); ``reset(draws=)`` takes [N, 4]."""
 
     metadata = {'render_modes': [], 'render_fps': 50}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "construction", cabi.MgxConstructionEnv, OBS_DIM, 4
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0):
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = construction_model()
-        self.tables = ConstructionTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = construction_model()
+        self._setup(num_envs, device, precision, model, ConstructionTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dev, N = self.device, num_envs
         self.scal = torch.zeros(N, 4, dtype=torch.float64, device=dev)   # progress, wind, rain, temperature
         self.ints = torch.zeros(N, 5, dtype=torch.int32, device=dev)     # task, step, blocks, violations, completed
@@ -110,50 +98,9 @@ class ConstructionVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding,
         # or float64 once a float64 action's reward was added; total_kind records which (include/mgx.h)
         self.total_reward = torch.zeros(N, dtype=torch.float64, device=dev)
         self.total_kind = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.rollout = torch.zeros(N, 4, dtype=torch.float64, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxConstructionEnv(*[t.data_ptr() for t in (self.scal, self.ints, self.total_reward,
-                                                                      self.episode, self.rollout)])
-        self._env.total_kind = self.total_kind.data_ptr()
-        ids = self.tables.ids_struct()
-        check(lib().mgx_construction_configure(self.native.handle, C.byref(ids)), "mgx_construction_configure")
+        self._bind(self.scal, self.ints, self.total_reward, self.episode, self.rollout, total_kind=self.total_kind)
         self.action_space = Box(low=-ACTION_LIMIT, high=ACTION_LIMIT, shape=(self.model.nu,), dtype=np.float32)
-
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,4] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 4), dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_construction_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                           _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs,
-                                           _ptr(env_mask), stream_handle(stream)), "mgx_construction_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step for every env. ``actions`` [N, nu] float32 or float64 (clipped to +-200)."""
-        # float32, or float64: the reference's np.clip keeps a float64 policy's dtype, so ctrl and the
-        # action terms of the reward follow in float64 (include/mgx.h action_f64)
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        assert actions.shape == (self.num_envs, self.model.nu), actions.shape
-        check(lib().mgx_construction_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                          _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                          _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                          1 if self.autoreset else 0, self.seed_value, self.env_offset,
-                                          self.num_envs, None, stream_handle(stream)), "mgx_construction_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (construction_env.py:739-752)."""
@@ -171,11 +118,8 @@ class ConstructionVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding,
             'bad_state_resets': self.batch.warning,
         }
 
-    def close(self):
-        pass
 
-
-class HumanoidConstructionEnv(EnvBase):
+class HumanoidConstructionEnv(TaskEnv):
     """Drop-in for humanoid_construction_env.construction_env.HumanoidConstructionEnv on libmgx.
     A float32 action (``action_space.sample()``, float32 policies) is clipped against the float32
     bounds in float32, and the reward is np.float32; a float64 action (or a list of floats) stays
@@ -208,31 +152,21 @@ class HumanoidConstructionEnv(EnvBase):
         self.np_random = None
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.current_step = 0
         self._total_before = 0.0
-        return obs[0].cpu().numpy().copy(), self._info()
+        return obs, self._info()
 
     def step(self, action: np.ndarray):
         act = policy_action(action)
-        a = torch.from_numpy(act.reshape(1, -1)).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        obs, rew, term, trunc = self._step_vec(act)
         self.current_step = int(self._vec.ints[0, 1])
         info = self._info()  # the total as it was before this step's reward (construction_env.py:614-617)
         kind = int(self._vec.total_kind[0])
         self._total_before = (np.float64 if kind == 1 else np.float32)(self._vec.total_reward[0].item())
         rtype = np.float64 if act.dtype == np.float64 else np.float32
-        return obs[0].cpu().numpy().copy(), rtype(rew[0].item()), bool(term[0]), bool(trunc[0]), info
+        return obs, rtype(rew), term, trunc, info
 
     def _info(self) -> Dict[str, Any]:
         v = self._vec
@@ -243,9 +177,3 @@ class HumanoidConstructionEnv(EnvBase):
         return {'task': self.current_task, 'task_progress': float(sc[0]), 'blocks_placed': int(it[2]),
                 'safety_violations': int(it[3]), 'episode_stats': stats,
                 'weather': {'wind': float(sc[1]), 'rain': float(sc[2]), 'temperature': float(sc[3])}}
-
-    def render(self):
-        return None  # no viewer on a headless GPU node
-
-    def close(self):
-        self.viewer = None

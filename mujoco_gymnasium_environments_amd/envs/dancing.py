@@ -19,24 +19,16 @@ joint: the torso hangs from the world through the abdomen hinges), 16 bodies, 17
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "humanoid_dancing.xml")
 MOVES = ['basic_step', 'spin', 'jump', 'moonwalk', 'robot_wave', 'freeze', 'hip_hop_bounce', 'breakdance_toprock',
@@ -116,23 +108,19 @@ class DancingTables:
         return np.array(d)
 
 
-class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU."""
+class DancingVectorEnv(TaskVectorEnv):
+    """``num_envs`` humanoid_dancing envs stepping in lockstep on one GPU, one RK4 mj_step per env
+    step. ``step(actions)`` takes [N, 29]; ``reset(draws=)`` takes [N, 40]."""
 
     metadata = {'render_modes': [], 'render_fps': 60}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "dancing", cabi.MgxDancingEnv, OBS_DIM, 2 * SEQ_LEN
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0,
                  rows_in_scratch: Optional[bool] = None):
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = dancing_model(rows_in_scratch)
-        self.tables = DancingTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = dancing_model(rows_in_scratch)
+        self._setup(num_envs, device, precision, model, DancingTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dev, N = self.device, num_envs
         self.scal = torch.zeros(N, 18, dtype=torch.float64, device=dev)
         self.scal[:, 2:5] = torch.tensor([0.0, 0.0, 5.0], dtype=torch.float64)   # spotlight (dancing_env.py:95)
@@ -143,54 +131,14 @@ class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
         self.moves = torch.zeros(N, SEQ_LEN, dtype=torch.int32, device=dev)
         self.durations = torch.zeros(N, SEQ_LEN, dtype=torch.float64, device=dev)
         self.prev_jvel = torch.zeros(N, self.model.nv - 6, dtype=torch.float64, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.rollout = torch.zeros(N, 4, dtype=self.batch.dtype, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxDancingEnv(*[t.data_ptr() for t in (
-            self.scal, self.ints, self.hist, self.moves, self.durations, self.prev_jvel, self.episode, self.rollout)])
-        ids = self.tables.ids_struct()
-        check(lib().mgx_dancing_configure(self.native.handle, C.byref(ids)), "mgx_dancing_configure")
+        self._bind(self.scal, self.ints, self.hist, self.moves, self.durations, self.prev_jvel, self.episode,
+                   self.rollout)
         self.action_space = Box(low=-ACTION_LIMIT, high=ACTION_LIMIT, shape=(N_ACT,), dtype=np.float32)
 
     @property
     def step_count(self) -> torch.Tensor:
         return self.ints[:, 0]
-
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,40] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 2 * SEQ_LEN),
-                                dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_dancing_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                      _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs, _ptr(env_mask),
-                                      stream_handle(stream)), "mgx_dancing_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step (one RK4 mj_step) for every env. ``actions`` float32 [N, 29]."""
-        # float32, or float64: the reference's np.clip keeps a float64 policy's dtype, so ctrl and the
-        # action terms of the reward follow in float64 (include/mgx.h action_f64)
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        assert actions.shape == (self.num_envs, N_ACT), actions.shape
-        check(lib().mgx_dancing_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                     _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                     _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                     1 if self.autoreset else 0, self.seed_value, self.env_offset, self.num_envs,
-                                     None, stream_handle(stream)), "mgx_dancing_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (dancing_env.py:868-878)."""
@@ -208,11 +156,8 @@ class DancingVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
             'bad_state_resets': self.batch.warning,
         }
 
-    def close(self):
-        pass
 
-
-class HumanoidDancingEnv(EnvBase):
+class HumanoidDancingEnv(TaskEnv):
     """Drop-in for humanoid_dancing_env.dancing_env.HumanoidDancingEnv, simulated by libmgx."""
 
     metadata = {'render_modes': ['human', 'rgb_array'], 'render_fps': 60}
@@ -239,28 +184,17 @@ class HumanoidDancingEnv(EnvBase):
         self.current_step = 0
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.current_step = 0
         info = self._info()
-        return obs[0].cpu().numpy().copy(), {'episode_stats': info['episode_stats'],
-                                             'current_move': self.dance_moves[MOVES[0]], 'beat_phase': 0.0,
-                                             'combo_multiplier': info['combo_multiplier']}
+        return obs, {'episode_stats': info['episode_stats'], 'current_move': self.dance_moves[MOVES[0]],
+                     'beat_phase': 0.0, 'combo_multiplier': info['combo_multiplier']}
 
     def step(self, action: np.ndarray):
-        a = torch.from_numpy(policy_action(action).reshape(1, -1)).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        out = self._step_vec(action)
         self.current_step = int(self._vec.ints[0, 0])
-        return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), self._info()
+        return (*out, self._info())
 
     def _info(self) -> Dict[str, Any]:
         v = self._vec
@@ -272,12 +206,6 @@ class HumanoidDancingEnv(EnvBase):
         return {'episode_stats': stats, 'current_move': self.dance_moves[MOVES[int(it[3]) % len(MOVES)]],
                 'beat_phase': float(sc[0]) / BEAT, 'combo_multiplier': float(sc[5]),
                 'crowd_excitement': float(sc[8]), 'performance_score': float(sc[6])}
-
-    def render(self):
-        return None  # dancing_env.py:1294-1298 (viewer sync only)
-
-    def close(self):
-        self.viewer = None
 
 
 def register_envs() -> bool:

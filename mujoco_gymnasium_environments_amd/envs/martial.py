@@ -12,24 +12,16 @@ reward / termination / statistics for every env.
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets",
                      "humanoid_martial_arts.xml")
@@ -102,70 +94,27 @@ class MartialTables:
         return np.array([rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5)])
 
 
-class MartialArtsVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` humanoid_martial_arts envs stepping in lockstep on one GPU."""
+class MartialArtsVectorEnv(TaskVectorEnv):
+    """``num_envs`` humanoid_martial_arts envs stepping in lockstep on one GPU. ``step(actions)``
+    takes [N, nu] in [-1, 1] (clipped); ``reset(draws=)`` takes [N, 2]."""
 
     metadata = {'render_modes': [], 'render_fps': 60}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "martial", cabi.MgxMartialEnv, OBS_DIM, 2
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0,
                  rows_in_scratch: Optional[bool] = None):
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = martial_model(rows_in_scratch)
-        self.tables = MartialTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = martial_model(rows_in_scratch)
+        self._setup(num_envs, device, precision, model, MartialTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dev, N = self.device, num_envs
         # stance_stability_time, total_distance_moved, prev_torso_pos[3] (fp64)
         self.scal = torch.zeros(N, 5, dtype=torch.float64, device=dev)
         # current_step, techniques_performed, falls, has prev_torso_pos
         self.ints = torch.zeros(N, 4, dtype=torch.int32, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.rollout = torch.zeros(N, 4, dtype=torch.float64, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxMartialEnv(*[t.data_ptr() for t in (self.scal, self.ints, self.episode, self.rollout)])
-        ids = self.tables.ids_struct()
-        check(lib().mgx_martial_configure(self.native.handle, C.byref(ids)), "mgx_martial_configure")
+        self._bind(self.scal, self.ints, self.episode, self.rollout)
         self.action_space = Box(low=-1.0, high=1.0, shape=(self.model.nu,), dtype=np.float32)
-
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,2] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 2), dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_martial_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                      _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs, _ptr(env_mask),
-                                      stream_handle(stream)), "mgx_martial_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step for every env. ``actions`` float32 [N, nu] in [-1, 1] (clipped)."""
-        # float32, or float64: the reference's np.clip keeps a float64 policy's dtype, so ctrl and the
-        # action terms of the reward follow in float64 (include/mgx.h action_f64)
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        assert actions.shape == (self.num_envs, self.model.nu), actions.shape
-        check(lib().mgx_martial_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                     _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                     _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                     1 if self.autoreset else 0, self.seed_value, self.env_offset, self.num_envs,
-                                     None, stream_handle(stream)), "mgx_martial_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (martial_arts_env.py:623-630)."""
@@ -180,11 +129,8 @@ class MartialArtsVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, 
             'bad_state_resets': self.batch.warning,
         }
 
-    def close(self):
-        pass
 
-
-class HumanoidMartialArtsEnv(EnvBase):
+class HumanoidMartialArtsEnv(TaskEnv):
     """Drop-in for humanoid_martial_arts_env.martial_arts_env.HumanoidMartialArtsEnv on libmgx.
     Actions are taken as float32 (the reference keeps the caller's dtype through np.clip; its
     energy term is float32 for float32 actions, e.g. action_space.sample())."""
@@ -208,25 +154,15 @@ class HumanoidMartialArtsEnv(EnvBase):
         self.np_random = None
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.current_step = 0
-        return obs[0].cpu().numpy().copy(), self._info()
+        return obs, self._info()
 
     def step(self, action: np.ndarray):
-        a = torch.from_numpy(policy_action(action).reshape(1, -1)).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        out = self._step_vec(action)
         self.current_step = int(self._vec.ints[0, 0])
-        return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), self._info()
+        return (*out, self._info())
 
     def _info(self) -> Dict[str, Any]:
         v = self._vec
@@ -235,9 +171,3 @@ class HumanoidMartialArtsEnv(EnvBase):
         stats = dict(zip(STAT_KEYS, [int(it[1]), 0, 0, 0, float(sc[1]), int(it[2])]))
         return {'episode_stats': stats, 'combo_chain': [], 'stance_stability': float(sc[0]),
                 'current_step': int(it[0])}
-
-    def render(self):
-        return None  # no viewer on a headless GPU node
-
-    def close(self):
-        self.viewer = None

@@ -12,24 +12,16 @@ Both run one fused HIP launch per env step (libmgx.so ``mgx_parkour_step``): act
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import NativeError, check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase, policy_action
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 from .sharded import StreamShardedEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "quadruped_parkour.xml")
@@ -117,10 +109,14 @@ class ParkourTables:
         return np.array([rng.uniform(-1.5, 1.5), rng.uniform(-1.0, 1.0)])
 
 
-class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` quadruped_parkour envs stepping in lockstep on one GPU."""
+class ParkourVectorEnv(TaskVectorEnv):
+    """``num_envs`` quadruped_parkour envs stepping in lockstep on one GPU, 10 physics substeps per
+    env step. ``step(actions)`` takes [N, 16] float32, or float64: a float64 action is clipped and
+    applied in float64 and its effort term follows in float64 (parkour_env.py:360-364, :702);
+    ``reset(draws=)`` takes [N, 2]."""
 
     metadata = {'render_modes': [], 'render_fps': 100}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "parkour", cabi.MgxParkourEnv, OBS_DIM, 2
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0,
@@ -129,15 +125,9 @@ class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
         ``banks`` precomputed resets per env (one covers every autoreset: a bank settles within one
         env step); ``staged=False`` runs one wave per env for the whole env step. Both compute the
         same step (tests/test_gpu_parkour.py)."""
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = parkour_model(rows_in_scratch)
-        self.tables = ParkourTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = parkour_model(rows_in_scratch)
+        self._setup(num_envs, device, precision, model, ParkourTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dt, dev, N = self.batch.dtype, self.device, num_envs
         self.last_position = torch.zeros(N, 3, dtype=dt, device=dev)
         self.max_progress = torch.zeros(N, dtype=dt, device=dev)
@@ -147,68 +137,16 @@ class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
         self.fall_count = torch.zeros(N, dtype=torch.int32, device=dev)
         self.stuck = torch.zeros(N, dtype=torch.int32, device=dev)
         self.step_count = torch.zeros(N, dtype=torch.int32, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.rollout = torch.zeros(N, 4, dtype=dt, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxParkourEnv(*[t.data_ptr() for t in (
-            self.last_position, self.max_progress, self.episode_reward, self.er_kind, self.reached, self.fall_count,
-            self.stuck, self.step_count, self.episode, self.rollout)])
-        ids = self.tables.ids_struct()
-        check(lib().mgx_parkour_configure(self.native.handle, C.byref(ids)), "mgx_parkour_configure")
-        self.workspace = None
-        nb = int(lib().mgx_parkour_workspace_bytes(self.native.handle, N, banks)) if staged else 0
-        if staged and nb == cabi.MGX_E_UNSUPPORTED:
-            # a model / hook configuration the staged pipeline does not take (e.g. a solver layout
-            # that would need a second launch): the monolithic step computes the same physics at
-            # the same capacity (tests/test_gpu_parkour.py runs both)
-            staged = False
-        self.staged = staged
+        self._bind(self.last_position, self.max_progress, self.episode_reward, self.er_kind, self.reached,
+                   self.fall_count, self.stuck, self.step_count, self.episode, self.rollout)
         if staged:
-            if nb <= 0:
-                raise NativeError(f"mgx_parkour_workspace_bytes: {lib().mgx_last_error().decode()}")
-            self.workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-            check(lib().mgx_parkour_workspace_init(self.native.handle, _ptr(self.workspace), nb, N, banks, None),
-                  "mgx_parkour_workspace_init")
-            self._env.workspace = self.workspace.data_ptr()
-            self._env.workspace_bytes = nb
-            self._env.banks = banks
+            # not for a model / hook configuration the staged pipeline does not take (e.g. a solver
+            # layout that would need a second launch): the monolithic step computes the same physics
+            # at the same capacity (tests/test_gpu_parkour.py runs both)
+            self._stage(banks, optional=True)
         lim = action_limits()
         self.action_space = Box(low=-lim, high=lim, dtype=np.float32)
-
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,2] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 2), dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_parkour_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                      _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs, _ptr(env_mask),
-                                      stream_handle(stream)), "mgx_parkour_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step (10 physics substeps) for every env. ``actions`` [N, 16] float32, or float64:
-        a float64 action is clipped and applied in float64 and its effort term follows in float64,
-        as the reference's np.clip keeps a float64 policy's dtype (parkour_env.py:360-364, :702)."""
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        assert actions.shape == (self.num_envs, 16), actions.shape
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        check(lib().mgx_parkour_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                     _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                     _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                     1 if self.autoreset else 0, self.seed_value, self.env_offset, self.num_envs,
-                                     None, stream_handle(stream)), "mgx_parkour_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict (parkour_env.py:797-815). Views only
@@ -233,9 +171,6 @@ class ParkourVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Tran
     def course_completion(self) -> torch.Tensor:
         x = self.last_position[:, 0].double()
         return ((x - START_POS[0]) / (FINISH_POS[0] - START_POS[0])).clamp(0.0, 1.0)
-
-    def close(self):
-        pass
 
 
 class StreamShardedParkourEnv(StreamShardedEnv):
@@ -266,7 +201,7 @@ def _popcount(x: torch.Tensor) -> torch.Tensor:
     return c
 
 
-class QuadrupedParkourEnv(EnvBase):
+class QuadrupedParkourEnv(TaskEnv):
     """Drop-in for quadruped_parkour_env.parkour_env.QuadrupedParkourEnv, simulated by libmgx."""
 
     metadata = {'render_modes': ['human', 'rgb_array'], 'render_fps': 100}
@@ -301,25 +236,15 @@ class QuadrupedParkourEnv(EnvBase):
         self.step_count = 0
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.step_count = 0
-        return obs[0].cpu().numpy().copy(), self._info()
+        return obs, self._info()
 
     def step(self, action: np.ndarray):
-        a = torch.from_numpy(policy_action(action).reshape(1, -1)).to(self._vec.device)  # clipped on the device
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        out = self._step_vec(action)
         self.step_count = int(self._vec.step_count[0])
-        return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), self._info()
+        return (*out, self._info())
 
     def _info(self) -> Dict[str, Any]:
         v = self._vec
@@ -337,9 +262,6 @@ class QuadrupedParkourEnv(EnvBase):
         if self.render_mode == 'rgb_array':
             return np.zeros((480, 640, 3), dtype=np.uint8)  # parkour_env.py:835-837
         return None
-
-    def close(self):
-        self.viewer = None
 
 
 def register_envs() -> bool:

@@ -18,6 +18,8 @@ from typing import Any, Callable, Dict, Optional
 import numpy as np
 import torch
 
+from .base import device_actions
+
 
 class _CatInfo(Mapping):
     """info() of a stream-sharded batch: each field is the shards' device views concatenated on
@@ -111,9 +113,7 @@ class StreamShardedEnv:
 
     def step(self, actions: torch.Tensor, stream=None):
         """One env step for every env; actions float32 or float64 [N, nu] on the device."""
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
+        actions = device_actions(actions, self.device)
         assert actions.shape == (self.num_envs, self.nu), actions.shape
         self._fan_out(stream, lambda a, b, s, st: s.step(actions[a:b], stream=st))
         return self.obs, self.reward, self.terminated, self.truncated, self.info()

@@ -14,21 +14,15 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 from .. import cabi, mjcf
-from ..batch import PhysicsBatch, _ptr, stream_handle
-from ..native import NativeError, check, lib
-from ..dynamics import DynamicsForwarding
-from ..rollouts import RolloutForwarding
-from ..transitions import TransitionForwarding
-from ..rays import RayForwarding
-from ..sensors import SensorForwarding
-from ..seeding import np_random
-from ..spaces import Box, EnvBase
+from ..native import check, lib
+from ..spaces import Box
+from .base import TaskEnv, TaskVectorEnv
 from .sharded import StreamShardedEnv
 
 ASSET = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "humanoid_soccer.xml")
@@ -132,10 +126,13 @@ class SoccerTables:
         return out
 
 
-class SoccerVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
-    """``num_envs`` humanoid_soccer envs stepping in lockstep on one GPU."""
+class SoccerVectorEnv(TaskVectorEnv):
+    """``num_envs`` humanoid_soccer envs stepping in lockstep on one GPU. ``step(actions)`` takes
+    [N, nu] float32, or float64: a float64 action is clipped and applied in float64 and its energy
+    term summed in float64 (soccer_env.py:401-405, :674); ``reset(draws=)`` takes [N, 36]."""
 
     metadata = {'render_modes': [], 'render_fps': 50}
+    TASK, ENV_STRUCT, OBS_DIM, N_DRAWS = "soccer", cabi.MgxSoccerEnv, OBS_DIM, 36
 
     def __init__(self, num_envs: int, device: str = "cuda:0", precision: str = "f64", seed: int = 0,
                  max_episode_steps: int = MAX_EPISODE_STEPS, autoreset: bool = True, env_offset: int = 0,
@@ -150,15 +147,9 @@ class SoccerVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Trans
         if full_capacity and not staged:
             # the monolithic layout holds 64 contacts / 192 rows whatever the model's capacity
             raise ValueError("full_capacity needs the staged pipeline (staged=True)")
-        self.num_envs = num_envs
-        self.device = torch.device(device)
-        self.model = soccer_model(full_capacity)
-        self.tables = SoccerTables(self.model, max_episode_steps)
-        self.batch = PhysicsBatch(self.model, num_envs, precision=precision, device=device)
-        self.native = self.batch.native
-        self.autoreset = autoreset
-        self.seed_value = int(seed) & ((1 << 64) - 1)
-        self.env_offset = env_offset
+        model = soccer_model(full_capacity)
+        self._setup(num_envs, device, precision, model, SoccerTables(model, max_episode_steps), autoreset, seed,
+                    env_offset)
         dt, dev, N = self.batch.dtype, self.device, num_envs
         self.prev_ball_pos = torch.zeros(N, 3, dtype=dt, device=dev)
         self.prev_robot_pos = torch.zeros(N, 3, dtype=dt, device=dev)
@@ -166,71 +157,20 @@ class SoccerVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Trans
         self.step_count = torch.zeros(N, dtype=torch.int32, device=dev)
         self.goal_scored = torch.zeros(N, dtype=torch.uint8, device=dev)
         self.stats = torch.zeros(N, 5, dtype=dt, device=dev)
-        self.episode = torch.zeros(N, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
         # running sums: reward, terminated, truncated, steps, nefc, PGS sweeps, nefc^2,
         # sweeps * nefc^2 (include/mgx.h mgx_soccer_env.rollout)
         self.rollout = torch.zeros(N, 8, dtype=torch.float64, device=dev)
-        self.obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.final_obs = torch.zeros(N, OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self._env = cabi.MgxSoccerEnv(*[t.data_ptr() for t in (self.prev_ball_pos, self.prev_robot_pos, self.wind,
-                                                               self.step_count, self.goal_scored, self.stats,
-                                                               self.episode, self.flags, self.rollout)])
-        self.staged = staged
-        self.workspace = None
-        if staged:
-            nb = int(lib().mgx_soccer_workspace_bytes(self.native.handle, N, banks))
-            if nb <= 0:
-                raise NativeError(f"mgx_soccer_workspace_bytes: {lib().mgx_last_error().decode()}")
-            self.workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-            check(lib().mgx_soccer_workspace_init(self.native.handle, _ptr(self.workspace), nb, N, banks, None),
-                  "mgx_soccer_workspace_init")
-            self._env.workspace = self.workspace.data_ptr()
-            self._env.workspace_bytes = nb
-            self._env.banks = banks
-        ids = self.tables.ids_struct()
-        check(lib().mgx_soccer_configure(self.native.handle, C.byref(ids)), "mgx_soccer_configure")
+        self._bind(self.prev_ball_pos, self.prev_robot_pos, self.wind, self.step_count, self.goal_scored, self.stats,
+                   self.episode, self.flags, self.rollout)
         nq = np.array([int(self.model.jnt_qposadr[j]) for j in self.tables.noise_joints], dtype=np.int32)
         nr = np.array([self.model.jnt_range[j] for j in self.tables.noise_joints], dtype=np.float64).reshape(-1)
         check(lib().mgx_soccer_configure_reset(self.native.handle, self.tables.root_qposadr, len(nq),
                                                nq.ctypes.data_as(C.POINTER(C.c_int32)),
                                                nr.ctypes.data_as(C.POINTER(C.c_double))), "configure_reset")
+        if staged:
+            self._stage(banks)
         self.action_space = Box(low=-150.0, high=150.0, shape=(self.model.nu,), dtype=np.float32)
-
-    # ------------------------------------------------------------------ API
-    def reset(self, seed: Optional[int] = None, env_mask: Optional[torch.Tensor] = None,
-              draws: Optional[np.ndarray] = None, stream=None) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        """reset() for all (or masked) envs. ``draws`` [N,36] (host, reference order) gives exact
-        gymnasium seeding; otherwise device Philox draws keyed by (seed, env, episode)."""
-        if seed is not None:
-            self.seed_value = int(seed) & ((1 << 64) - 1)
-            self.episode.zero_()
-        d = None
-        if draws is not None:
-            d = torch.as_tensor(np.asarray(draws).reshape(self.num_envs, 36), dtype=self.batch.dtype).to(self.device)
-        check(lib().mgx_soccer_reset(self.native.handle, C.byref(self.batch.state), C.byref(self._env), _ptr(d),
-                                     _ptr(self.obs), self.seed_value, self.env_offset, self.num_envs, _ptr(env_mask),
-                                     stream_handle(stream)), "mgx_soccer_reset")
-        return self.obs, self.info()
-
-    def step(self, actions: torch.Tensor, stream=None):
-        """One env step for every env. ``actions`` [N, nu] on the device: float32, or float64 — a
-        float64 action is clipped and applied in float64 and its energy term summed in float64,
-        as the reference's np.clip keeps a float64 policy's dtype (soccer_env.py:401-405, :674)."""
-        dt = torch.float64 if actions.dtype == torch.float64 else torch.float32
-        if actions.dtype != dt or not actions.is_contiguous() or actions.device != self.device:
-            actions = actions.to(device=self.device, dtype=dt).contiguous()
-        assert actions.shape == (self.num_envs, self.model.nu), actions.shape
-        self._env.action_f64 = 1 if dt == torch.float64 else 0
-        check(lib().mgx_soccer_step(self.native.handle, C.byref(self.batch.state), C.byref(self._env),
-                                    _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
-                                    _ptr(self.truncated), _ptr(self.final_obs) if self.autoreset else None,
-                                    1 if self.autoreset else 0, self.seed_value, self.env_offset, self.num_envs,
-                                    None, stream_handle(stream)), "mgx_soccer_step")
-        return self.obs, self.reward, self.terminated, self.truncated, self.info()
 
     def info(self) -> Dict[str, Any]:
         """Device-tensor views of the reference's info dict fields (soccer_env.py:433-441)."""
@@ -245,9 +185,6 @@ class SoccerVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, Trans
             'episode': self.episode,
             'bad_state_resets': self.batch.warning,
         }
-
-    def close(self):
-        pass
 
 
 class StreamShardedSoccerEnv(StreamShardedEnv):
@@ -277,7 +214,7 @@ def _obs_bounds(num_joints: int):
     return low, high
 
 
-class HumanoidSoccerEnv(EnvBase):
+class HumanoidSoccerEnv(TaskEnv):
     """Drop-in for humanoid_soccer_env.soccer_env.HumanoidSoccerEnv, simulated by libmgx."""
 
     metadata = {'render_modes': ['human', 'rgb_array', 'depth_array'], 'render_fps': 50}
@@ -303,28 +240,16 @@ class HumanoidSoccerEnv(EnvBase):
         self.np_random = None
         self.seed()
 
-    def seed(self, seed: Optional[int] = None) -> list:
-        self.np_random, seed = np_random(seed)
-        return [seed]
-
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
-        if seed is not None:
-            self.seed(seed)
-        draws = self._vec.tables.reset_draws(self.np_random)[None]
-        obs, _ = self._vec.reset(draws=draws)
-        torch.cuda.synchronize(self._vec.device)
+        obs = self._reset_vec(seed)
         self.current_step = 0
-        return obs[0].cpu().numpy().copy(), self._info(False)
+        return obs, self._info(False)
 
     def step(self, action: np.ndarray):
         # np.clip against the float32 bounds keeps a float64 action float64 (soccer_env.py:401-405)
-        action = np.clip(np.asarray(action), self.action_space.low, self.action_space.high)
-        action = action.astype(np.float64 if action.dtype == np.float64 else np.float32, copy=False)
-        a = torch.from_numpy(np.ascontiguousarray(action.reshape(1, -1))).to(self._vec.device)
-        obs, rew, term, trunc, _ = self._vec.step(a)
-        torch.cuda.synchronize(self._vec.device)
+        out = self._step_vec(np.clip(np.asarray(action), self.action_space.low, self.action_space.high))
         self.current_step = int(self._vec.step_count[0])
-        return (obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0]), self._info(True))
+        return (*out, self._info(True))
 
     def _info(self, stepped: bool) -> Dict[str, Any]:
         v = self._vec
@@ -342,12 +267,6 @@ class HumanoidSoccerEnv(EnvBase):
             info.update({'ball_contact': bool(fl[0]), 'robot_upright': bool(fl[1]),
                          'goal_scored': bool(v.goal_scored[0])})
         return info
-
-    def render(self):
-        return None  # no viewer on a headless GPU node
-
-    def close(self):
-        self.viewer = None
 
 
 def register_envs() -> bool:

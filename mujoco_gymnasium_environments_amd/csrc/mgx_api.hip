@@ -68,7 +68,7 @@ __device__ __forceinline__ void soccer_reset_philox(const DevModel<T>& m, Env<T>
     ev.episode[env] = E + 1;
   }
   wsync();
-  if (P) bank_init(m, e, ids, *P, env, E % P->R, E + P->R, seed, env_offset);
+  if (P) bank_init<SoccerBank<T>>(m, e, ids, *P, env, env * P->R + E % P->R, E + P->R, seed, env_offset);
 }
 
 // One full soccer step of `env` in one wave (pre, mj_step, post, same-step autoreset).
@@ -109,7 +109,7 @@ __device__ __forceinline__ void soccer_step_mono(const DevModel<T>& m, Env<T>& e
       for (int i = l; i < 80; i += 64) final_obs[(size_t)env * 80 + i] = o[i];
     __threadfence();
     wsync();
-    if (!(P && bank_install(m, e, ids, *P, s, ev, obs, seed, env_offset, env)))
+    if (!(P && bank_install<SoccerBank<T>>(m, e, ids, *P, s, ev, obs, seed, env_offset, env)))
       soccer_reset_philox(m, e, ids, s, ev, obs, seed, env_offset, env, P);
   }
 }
@@ -157,24 +157,11 @@ __global__ void __launch_bounds__(64) k_soccer_template(DevModel<T> m, Pipe P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Env<T> e;
   env_bind(m, e, smem);
-  int l = lane_id();
   reset_env(m, e);
   forward(m, e);
   e.qacc_ws = e.qacc;
   euler(m, e);
-  for (int k = l; k < m.nq; k += 64) P.at<T>(P.o_tq)[k] = e.qpos[k];
-  for (int k = l; k < m.nv; k += 64) { P.at<T>(P.o_tv)[k] = e.qvel[k]; }
-  if (l < m.nv) P.at<T>(P.o_ta)[l] = e.qacc_ws;
-  for (int k = l; k < 3 * m.nbody; k += 64) { P.at<T>(P.o_tx)[k] = e.xpos[k]; P.at<T>(P.o_tsc)[k] = e.subtree_com[k]; }
-  for (int k = l; k < 4 * m.nbody; k += 64) P.at<T>(P.o_txq)[k] = e.xquat[k];
-  int nc = e.ncon < P.maxC ? e.ncon : P.maxC;
-  for (int k = l; k < nc; k += 64) {
-    P.at<int>(P.o_tcg)[2 * k] = e.con_geom[2 * k];
-    P.at<int>(P.o_tcg)[2 * k + 1] = e.con_geom[2 * k + 1];
-    P.at<T>(P.o_tcd)[k] = e.con_dist[k];
-    P.at<T>(P.o_tcm)[k] = e.con_mu[k];
-  }
-  if (l == 0) { P.at<int>(P.o_tn)[0] = nc; P.at<T>(P.o_tt)[0] = e.time; }
+  template_store(m, e, P);
 }
 
 // Env-logic-only test hook: frames/contacts come from the caller (golden vectors generated
@@ -734,8 +721,45 @@ size_t mgx::make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks,
   if (P) *P = p;
   return off;
 }
-static size_t make_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe* P) {
-  return make_staged_pipe(m, ws, n_env, banks, P, false, 80, MGX_PGS_SPLIT_BLOCKS);
+
+// The workspace entries of a staged task (StagedTask, mgx_internal.h)
+size_t mgx::task_pipe(const StagedTask& t, const mgx_model* m, void* ws, int n_env, int banks, Pipe* P) {
+  return make_staged_pipe(m, ws, n_env, banks, P, t.rk, t.nobs, t.split_default);
+}
+int mgx::task_pipe_checked(const StagedTask& t, const mgx_model* m, void* ws, uint64_t ws_bytes, int n_env, int banks,
+                           Pipe* P, size_t* need) {
+  const size_t n = task_pipe(t, m, ws, n_env, banks, P);
+  if (need) *need = n;
+  if (ws_bytes < n)
+    return host_fail(MGX_E_ARG, std::string("workspace smaller than mgx_") + t.name + "_workspace_bytes");
+  return MGX_OK;
+}
+int mgx::staged_check(const StagedTask& t, const mgx_model* m, int banks) {
+  if (!t.ok(m)) return host_fail(MGX_E_UNSUPPORTED, t.refusal);
+  if (banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "banks must be in [0, 16]");
+  return MGX_OK;
+}
+int64_t mgx::staged_workspace_bytes(const StagedTask& t, const mgx_model* m, int n_env, int banks) {
+  if (!m || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
+  if (!t.ok(m)) return host_fail(MGX_E_UNSUPPORTED, t.refusal);
+  return (int64_t)task_pipe(t, m, nullptr, n_env, banks, nullptr);
+}
+int mgx::staged_workspace_init(const StagedTask& t, const mgx_model* m, void* workspace, uint64_t bytes, int n_env,
+                               int banks, hipStream_t st) {
+  if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
+  if (t.init_checks && !t.ok(m)) return host_fail(MGX_E_UNSUPPORTED, t.refusal);
+  Pipe P;
+  size_t need;
+  if (int rc = task_pipe_checked(t, m, workspace, bytes, n_env, banks, &P, &need)) return rc;
+  MGX_HIPCHK(hipMemsetAsync(workspace, 0, need, st));
+  const size_t nb = (size_t)n_env * (banks > 0 ? banks : 1);
+  MGX_HIPCHK(hipMemsetAsync(P.base + P.o_bk, 0xFF, nb * 4, st));  // bank settle counters = -1 (empty)
+  // the checkAcc template (load_template), once per workspace
+  const int gB = m->L.gB ? 1 : 0;
+  if (m->precision == MGX_F32) hipLaunchKernelGGL(t.template_f32[gB], dim3(1), dim3(64), m->L.bytes, st, m->mf, P);
+  else hipLaunchKernelGGL(t.template_f64[gB], dim3(1), dim3(64), m->L.bytes, st, m->md, P);
+  MGX_HIPCHK(hipGetLastError());
+  return MGX_OK;
 }
 
 // LDS of one solver wave holding `rows` rows per slot (main launch: min(max_nefc,
@@ -800,13 +824,8 @@ mgx::Hooks mgx::read_hooks() {
   return h;
 }
 
-// A side stream and two events per caller stream (created once, kept for the process): the wide
-// solver launch runs beside the main one. nullptr if the runtime refuses (then both run in order).
-struct SideStream {
-  hipStream_t s;
-  hipEvent_t rows, big;
-};
-static SideStream* side_stream(hipStream_t st) {
+// the side stream of a caller stream (mgx_internal.h)
+SideStream* mgx::side_stream(hipStream_t st) {
   static std::mutex mu;
   static std::map<std::pair<hipStream_t, int>, SideStream*> cache;
   int dev = 0;
@@ -868,13 +887,17 @@ static Pipe bank_view(const Pipe& P) {
   return B;
 }
 
-// LDS of the one-wave settle: the row builder's layout, then one solver wave with maxE rows per
-// slot, then the finisher's layout, in turn
+int mgx::staged_settle_lds(const mgx_model* m, const Pipe& P, int lps, int sqg, int twl) {
+  return std::max({staged_pgs_lds_bytes(m, P.maxE, lps, sqg, twl), m->Ls.bytes, m->Lf.bytes});
+}
+// soccer's workspace_init has never refused a model outside the staged pipeline (init_checks)
+static const StagedTask kSoccerStaged = {"soccer", [](const mgx_model* m) { return m->staged_ok; },
+                                         "staged step: model exceeds the staged solver's capacity", false, false, 80,
+                                         MGX_PGS_SPLIT_BLOCKS,
+                                         {k_soccer_template<float>, k_soccer_template<float>},
+                                         {k_soccer_template<double>, k_soccer_template<double>}};
 static int settle_lds_bytes(const mgx_model* m, const Pipe& P) {
-  int b = pgs_lds_bytes(m, P.maxE);
-  if (m->Ls.bytes > b) b = m->Ls.bytes;
-  if (m->Lf.bytes > b) b = m->Lf.bytes;
-  return b;
+  return staged_settle_lds(m, P, pgs_lanes(), 0, mgx_twl(false));
 }
 
 template <typename T>
@@ -885,13 +908,12 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
                               hipStream_t st) {
   Pipe P;
   int banks = autoreset ? e->banks : 0;
-  size_t need = make_pipe(m, e->workspace, n_env, e->banks, &P);
-  if (e->workspace_bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
+  if (int rc = task_pipe_checked(kSoccerStaged, m, e->workspace, e->workspace_bytes, n_env, e->banks, &P)) return rc;
   int slots = n_env * (1 + banks);
   const Hooks& H = m->hooks;
   // occupancy probe: MGX_ROWS_LDS pads the row builder's LDS (fewer waves per CU; up to 64 KiB)
   const int rlds = H.rows_lds > m->Ls.bytes && H.rows_lds <= 64 * 1024 ? H.rows_lds : m->Ls.bytes;
-  T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+  const T scale = staged_scale(M);
   // The bank pipeline (MGX_BANK_STREAM): the bank slots are not needed by this step and their
   // chains are short, while the live envs' longest chain sets the solver launch's length and
   // leaves most of the GPU idle at its end. So the bank slots' rows -> PGS -> bank finisher run on
@@ -974,9 +996,8 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
     MGX_HIPCHK(hipStreamWaitEvent(st, bmode == 1 ? bs->done : bs->rows, 0));
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                             env_offset, n_env, mask, P, banks, m->Lf.bytes, st, false, tail ? 2 : 0);
-    int fgrid = n_env < 256 ? n_env : 256;
     launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
-                            SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
+                            SETTLE_FIXUP, fixup_grid(n_env), settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
     if (bmode == 2) {
       MGX_HIPCHK(hipEventRecord(bs->live, st));
       MGX_HIPCHK(hipStreamWaitEvent(bs->s, bs->live, 0));
@@ -1014,9 +1035,8 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
     MGX_HIPCHK(hipStreamWaitEvent(st, tail->big, 0));
     launch_soccer_finish<T>(Mf, ids, *s, *e, action, obs, reward, terminated, truncated, final_obs, autoreset, seed,
                             env_offset, n_env, mask, P, banks, m->Lf.bytes, st, true, 2);
-    int fgrid = n_env < 256 ? n_env : 256;
     launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P,
-                            SETTLE_FIXUP, fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
+                            SETTLE_FIXUP, fixup_grid(n_env), settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
     MGX_HIPCHK(hipGetLastError());
     return MGX_OK;
   }
@@ -1038,9 +1058,8 @@ static int soccer_step_staged(const mgx_model* m, const DevModel<T>& M, const De
                           env_offset, n_env, mask, P, banks, m->Lf.bytes, st);
   // resets whose bank was not ready: settled in one wave each by the pipeline's own stages
   // (k_soccer_settle), a small grid-stride launch that exits at once when the list is empty
-  int fgrid = n_env < 256 ? n_env : 256;
   launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, (const T*)nullptr, obs, seed, env_offset, n_env, nullptr, P, SETTLE_FIXUP,
-                          fgrid, settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
+                          fixup_grid(n_env), settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
   MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
 }
@@ -1053,9 +1072,8 @@ static int soccer_reset_staged(const mgx_model* m, const DevModel<T>& M, const D
                                const SoccerIds<T>& ids, const mgx_state* s, const mgx_soccer_env* e, const T* draws,
                                float* obs, uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
-  size_t need = make_pipe(m, e->workspace, n_env, e->banks, &P);
-  if (e->workspace_bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
-  T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+  if (int rc = task_pipe_checked(kSoccerStaged, m, e->workspace, e->workspace_bytes, n_env, e->banks, &P)) return rc;
+  const T scale = staged_scale(M);
   launch_soccer_settle<T>(Ms, Mf, ids, *s, *e, draws, obs, seed, env_offset, n_env, mask, P, SETTLE_RESET, n_env,
                           settle_lds_bytes(m, P), st, M.iterations, M.tolerance, scale);
   MGX_HIPCHK(hipGetLastError());
@@ -1182,9 +1200,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
                              : mgx_set_lds(k_soccer_template<double>, m->L.bytes));
   if (r2 != MGX_OK) { delete m; return r2; }
   if (m->staged_ok) {
-    int sl = pgs_lds_bytes(m, m->Ls.max_nefc);  // the settle kernel's (settle_lds_bytes)
-    if (m->Ls.bytes > sl) sl = m->Ls.bytes;
-    if (m->Lf.bytes > sl) sl = m->Lf.bytes;
+    const int sl = std::max({pgs_lds_bytes(m, m->Ls.max_nefc), m->Ls.bytes, m->Lf.bytes});  // settle_lds_bytes
     r2 = staged_kernels_configure(precision, m->Ls.bytes, m->Lf.bytes, sl);
     if (r2 != MGX_OK) { delete m; return r2; }
     int pl = pgs_lds_bytes(m, m->Ls.max_nefc);  // the global-B launch's
@@ -1258,8 +1274,7 @@ int mgx_soccer_step(const mgx_model* m, const mgx_state* s, const mgx_soccer_env
     return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace) {
-    if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
-    if (e->banks < 0 || e->banks > 16) return host_fail(MGX_E_ARG, "banks must be in [0, 16]");
+    if (int rc = staged_check(kSoccerStaged, m, e->banks)) return rc;
     if (m->precision == MGX_F32)
       return soccer_step_staged<float>(m, m->mf, m->mfs, m->mff, m->sf, s, e, action, obs, reward, terminated,
                                        truncated, final_obs, autoreset, seed, env_offset, n_env, mask, st);
@@ -1275,8 +1290,7 @@ int mgx_soccer_reset(const mgx_model* m, const mgx_state* s, const mgx_soccer_en
   if (int rc = task_check_reset(kTask, m, s, e, obs, !draws, n_env)) return rc < 0 ? rc : MGX_OK;
   hipStream_t st = (hipStream_t)stream;
   if (e->workspace) {
-    if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
-    if (e->banks < 0 || e->banks > 16) return host_fail(MGX_E_ARG, "banks must be in [0, 16]");
+    if (int rc = staged_check(kSoccerStaged, m, e->banks)) return rc;
     if (m->precision == MGX_F32)
       return soccer_reset_staged<float>(m, m->mf, m->mfs, m->mff, m->sf, s, e, (const float*)draws, obs, seed,
                                         env_offset, n_env, mask, st);
@@ -1288,16 +1302,14 @@ int mgx_soccer_reset(const mgx_model* m, const mgx_state* s, const mgx_soccer_en
 }
 
 int64_t mgx_soccer_workspace_bytes(const mgx_model* m, int n_env, int banks) {
-  if (!m || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
-  return (int64_t)make_pipe(m, nullptr, n_env, banks, nullptr);
+  return staged_workspace_bytes(kSoccerStaged, m, n_env, banks);
 }
 
 int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_t* out, int n_out) {
   if (!m || !out || n_env <= 0 || banks < 0 || banks > 16 || n_out < 10) return host_fail(MGX_E_ARG, "bad argument");
   if (!m->staged_ok) return host_fail(MGX_E_UNSUPPORTED, "staged step: model exceeds the staged solver's capacity");
   Pipe P;
-  make_pipe(m, nullptr, n_env, banks, &P);
+  task_pipe(kSoccerStaged, m, nullptr, n_env, banks, &P);
   // [11], [12]: the bank view's counter block and arrival list (MGX_BANK_STREAM); [13], [14]: the
   // deferred-reset list and the row-split threshold in blocks (MGX_TAIL_FINISH)
   const int64_t v[15] = {(int64_t)P.o_ctr, (int64_t)P.o_ne, (int64_t)P.o_k2list, (int64_t)P.o_blk, (int64_t)P.o_B,
@@ -1308,20 +1320,7 @@ int mgx_soccer_workspace_layout(const mgx_model* m, int n_env, int banks, int64_
 }
 
 int mgx_soccer_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks, void* stream) {
-  if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return host_fail(MGX_E_ARG, "bad argument");
-  Pipe P;
-  size_t need = make_pipe(m, workspace, n_env, banks, &P);
-  if (bytes < need) return host_fail(MGX_E_ARG, "workspace smaller than mgx_soccer_workspace_bytes");
-  hipStream_t st = (hipStream_t)stream;
-  MGX_HIPCHK(hipMemsetAsync(workspace, 0, need, st));
-  size_t nb = (size_t)n_env * (banks > 0 ? banks : 1);
-  MGX_HIPCHK(hipMemsetAsync(P.base + P.o_bk, 0xFF, nb * 4, st));  // bank settle counters = -1 (empty)
-  if (m->precision == MGX_F32)
-    hipLaunchKernelGGL(k_soccer_template<float>, dim3(1), dim3(64), m->L.bytes, st, m->mf, P);
-  else
-    hipLaunchKernelGGL(k_soccer_template<double>, dim3(1), dim3(64), m->L.bytes, st, m->md, P);
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return staged_workspace_init(kSoccerStaged, m, workspace, bytes, n_env, banks, (hipStream_t)stream);
 }
 
 int mgx_soccer_logic_test(const mgx_model* m, const mgx_soccer_logic_io* io, int n_env, void* stream) {

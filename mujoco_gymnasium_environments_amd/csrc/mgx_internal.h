@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/mgx.h"
 #include "mgx_bipedal.h"
@@ -14,6 +15,7 @@
 #include "mgx_martial.h"
 #include "mgx_parkour.h"
 #include "mgx_staged.h"
+#include "mgx_bank.h"
 
 namespace mgx {
 // A/B and test hooks (MGX_* environment variables). Read once per model, in mgx_model_create, and
@@ -153,6 +155,56 @@ size_t make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe
 // sqg: row scalars in the pipe, only the forces in LDS (the RK4 pipeline; soccer at full capacity)
 // twl: block-table words per block in LDS (mgx_twl: 8 for the 8-dof group layout, 4 dof-granular)
 int staged_pgs_lds_bytes(const mgx_model* m, int rows, int lps, int sqg, int twl);
+// LDS of a one-wave settle: the row builder's layout, then one solver wave with maxE rows per slot,
+// then the finisher's layout, in turn
+int staged_settle_lds(const mgx_model* m, const Pipe& P, int lps, int sqg, int twl);
+// the solver's cost scale, 1 / (meaninertia * nv)
+template <typename T>
+T staged_scale(const DevModel<T>& M) {
+  return (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+}
+// waves of a settle kernel's fixup launch (grid-stride over the finisher's list; exits at once when
+// the list is empty)
+inline int fixup_grid(int n_env) { return n_env < 256 ? n_env : 256; }
+// f(std::integral_constant<int, E>) for the solver's register entries per lane E = epl in 1 .. 4
+template <typename F>
+void dispatch_epl(int epl, F&& f) {
+  switch (epl) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+// A side stream and two events per caller stream (created once, kept for the process): a solver
+// launch runs beside the main one. nullptr if the runtime refuses (then both run in order).
+struct SideStream {
+  hipStream_t s;
+  hipEvent_t rows, big;
+};
+SideStream* side_stream(hipStream_t st);
+// What a staged task's workspace entries differ in: its name in the messages, the model check and
+// its refusal (init_checks: mgx_<task>_workspace_init makes that check too), its make_staged_pipe
+// parameters and its checkAcc template kernels, indexed by Layout.gB
+struct StagedTask {
+  const char* name;
+  bool (*ok)(const mgx_model*);
+  const char* refusal;
+  bool init_checks;
+  bool rk;
+  int nobs, split_default;
+  void (*template_f32[2])(DevModel<float>, Pipe);
+  void (*template_f64[2])(DevModel<double>, Pipe);
+};
+size_t task_pipe(const StagedTask& t, const mgx_model* m, void* ws, int n_env, int banks, Pipe* P);
+// the pipe of a step / reset call over the env's workspace, refused when that is too small
+int task_pipe_checked(const StagedTask& t, const mgx_model* m, void* ws, uint64_t ws_bytes, int n_env, int banks, Pipe* P,
+                      size_t* need = nullptr);
+// a staged step / reset call's refusals: the model check, then the env's bank count
+int staged_check(const StagedTask& t, const mgx_model* m, int banks);
+int64_t staged_workspace_bytes(const StagedTask& t, const mgx_model* m, int n_env, int banks);
+int staged_workspace_init(const StagedTask& t, const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks,
+                          hipStream_t st);
 // the staged RK4 bipedal step (mgx_rk_staged.hip)
 int bipedal_staged_configure(const mgx_model* m);
 int bipedal_step_staged(const mgx_model* m, const mgx_state* s, const mgx_bipedal_env* e, const float* action, float* obs,

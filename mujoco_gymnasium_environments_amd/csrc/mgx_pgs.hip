@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(64) k_soccer_bank_finish(DevModel<T> m, Soccer
   }
   bank_store_state(m, e, P, bi, warn);
   k++;
-  if (k == 10) bank_finalize(m, e, ids, P, bi);
+  if (k == 10) SoccerBank<T>::finalize(m, e, ids, P, bi);
   if (lane_id() == 0) {
     P.at<int>(P.o_bk)[bi] = k;
     P.at<int>(P.o_bstg)[bi] = 0;
@@ -186,11 +186,8 @@ __global__ void __launch_bounds__(64) k_soccer_finish(DevModel<T> m, SoccerIds<T
     const int cnt = dl[0];
     for (int i = env - n_env; i < cnt; i += gridDim.x - n_env) {
       const int de = dl[1 + i];
-      bool ok = banks && bank_install(m, e, ids, P, s, ev, obs, seed, env_offset, de);
-      if (l == 0) {
-        atomicAdd(P.ctr() + 9, 1);
-        if (!ok) P.at<int>(P.o_fix)[atomicAdd(P.ctr(), 1)] = de * 4 + FIX_RESET;
-      }
+      bank_install_or_list<SoccerBank<T>>(m, e, ids, P, s, ev, obs, seed, env_offset, banks, de);
+      if (l == 0) atomicAdd(P.ctr() + 9, 1);
       wsync();
     }
     return;
@@ -249,15 +246,22 @@ __global__ void __launch_bounds__(64) k_soccer_finish(DevModel<T> m, SoccerIds<T
     }
     __threadfence();
     wsync();
-    bool ok = banks && bank_install(m, e, ids, P, s, ev, obs, seed, env_offset, env);
+    bank_install_or_list<SoccerBank<T>>(m, e, ids, P, s, ev, obs, seed, env_offset, banks, env);
     if (tier == 2 && l == 0) atomicAdd(P.ctr() + 10, 1);
-    if (!ok && l == 0) {
-      int i = atomicAdd(P.ctr(), 1);
-      P.at<int>(P.o_fix)[i] = env * 4 + FIX_RESET;
-    }
   }
 }
 
+// reset() and the resets whose bank was not ready: the bank layer's settle (mgx_bank.h) over this
+// translation unit's stages
+template <typename T, int EPL, int LPS>
+__global__ void __launch_bounds__(64) k_soccer_settle(DevModel<T> Ms, DevModel<T> Mf, SoccerIds<T> ids, mgx_state s,
+                                                      mgx_soccer_env ev, const T* draws, float* obs, uint64_t seed,
+                                                      int env_offset, int n_env, const uint8_t* mask, Pipe P, int mode,
+                                                      int maxit, T tol, T scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bank_settle<SoccerBank<T>, T, EPL, LPS>(Ms, Mf, ids, s, ev, draws, obs, seed, env_offset, n_env, mask, P, mode, maxit,
+                                          tol, scale, smem);
+}
 
 template <typename T>
 void launch_soccer_rows(const DevModel<T>& Ms, const SoccerIds<T>& ids, const mgx_state& s, const mgx_soccer_env& ev,
@@ -295,20 +299,15 @@ void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const So
   // the slots' flags in the carry are the pipeline's and do not hold for it
   Pipe P = Pin;
   P.qmh_pre = 0;
-#define MGX_SETTLE(E, L)                                                                                       \
-  hipLaunchKernelGGL((k_soccer_settle<T, E, L>), dim3(grid), dim3(64), lds, st, Ms, Mf, ids, s, ev, draws, obs, seed, \
-                     env_offset, n_env, mask, P, mode, maxit, tol, scale)
   if (pgs_lanes() == 64) {
-    MGX_SETTLE(1, 64);
+    hipLaunchKernelGGL((k_soccer_settle<T, 1, 64>), dim3(grid), dim3(64), lds, st, Ms, Mf, ids, s, ev, draws, obs, seed,
+                       env_offset, n_env, mask, P, mode, maxit, tol, scale);
   } else {
-    switch ((P.dpl + 1) / 2) {
-      case 1: MGX_SETTLE(1, 16); break;
-      case 2: MGX_SETTLE(2, 16); break;
-      case 3: MGX_SETTLE(3, 16); break;
-      default: MGX_SETTLE(4, 16); break;
-    }
+    dispatch_epl((P.dpl + 1) / 2, [&](auto epl) {
+      hipLaunchKernelGGL((k_soccer_settle<T, decltype(epl)::value, 16>), dim3(grid), dim3(64), lds, st, Ms, Mf, ids, s,
+                         ev, draws, obs, seed, env_offset, n_env, mask, P, mode, maxit, tol, scale);
+    });
   }
-#undef MGX_SETTLE
 }
 #define MGX_STAGED_INST(T)                                                                                              \
   template void launch_soccer_rows<T>(const DevModel<T>&, const SoccerIds<T>&, const mgx_state&, const mgx_soccer_env&, \

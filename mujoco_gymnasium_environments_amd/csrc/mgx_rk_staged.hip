@@ -20,9 +20,6 @@
 // launches. reset() and a reset whose bank is not ready run k_rk_settle: the same stages, in one
 // wave, through the same device code and flags (one translation unit), so a reset has one
 // arithmetic whatever the bank count.
-#include <map>
-#include <mutex>
-
 #include "mgx_internal.h"
 
 using namespace mgx;
@@ -37,7 +34,6 @@ constexpr int RK_LPS = 16;  // solver lanes per slot
 constexpr int RK_EPL = 4;   // solver register entries per lane (nv 49..64)
 constexpr int RK_OBS = 102; // rescue_env.py:545-600
 enum { RK_IDLE = 0, RK_ACTIVE = 1 };
-enum { RK_SETTLE_RESET = 0, RK_SETTLE_FIXUP = 1 };
 
 // per-slot RK4 carry (P.o_rk): X[0] positions, the next stage's positions, v[4][64], f[4][64], t0
 template <typename T>
@@ -58,93 +54,86 @@ __device__ __forceinline__ RkCarry<T> rk_carry(const DevModel<T>& m, const Pipe&
 }
 
 // ---------------------------------------------------------------- banks (bipedal)
-// record bi restarts for `episode` from 12 draws in LDS (rescue_env.py:473-508 after mj_resetData;
-// the task's tracking reset is applied when the bank is installed)
 template <typename T>
-__device__ __forceinline__ void rk_bank_init_draws(const DevModel<T>& m, Env<T>& e, const BipedalIds& ids, const Pipe& P,
-                                                   int bi, int episode, uint64_t seed, const T* draws) {
-  int l = lane_id();
-  T d[12];
-  for (int j = 0; j < 12; j++) d[j] = draws[j];
-  wsync();
-  reset_env(m, e);
-  if (l == 0) {
-    e.qpos[ids.root_x] = d[0];
-    e.qpos[ids.root_y] = d[1];
-    e.qpos[ids.root_z] = (T)1.2;
-    for (int i = 0; i < 5; i++) {
-      e.qpos[ids.victim_x[i]] = e.qpos[ids.victim_x[i]] + d[2 + 2 * i];
-      e.qpos[ids.victim_y[i]] = e.qpos[ids.victim_y[i]] + d[3 + 2 * i];
+__device__ __forceinline__ void rk_settle_step(const DevModel<T>& Ms, const DevModel<T>& Mf, const BipedalIds& ids,
+                                               mgx_state s, mgx_bipedal_env be, const Pipe& P, char* smem, int env,
+                                               int bi, int slot, int maxit, T tol, T scale);
+// What bipedal plugs into the bank layer (mgx_bank.h): a reset is mj_resetData and 12 draws
+// (rescue_env.py:473-508), ten RK4 settle steps (rescue_env.py:390-391), then the observation and
+// prev_robot_pos (rescue_env.py:393-396).
+template <typename T>
+struct BipedalBank {
+  typedef BipedalIds Ids;
+  typedef mgx_bipedal_env EnvT;
+  typedef const T* Draws;  // 12 draws in e.vec3 (LDS)
+  static constexpr int OBS = RK_OBS, DRAWS = 12;
+  static constexpr bool STG = false, STEP_COUNTS = true;
+  static constexpr int FIX_CTR = 5;  // k_pgs_groups clears [0] at every launch, four times per env step
+  __device__ static int fix_entry(int env) { return env; }
+  __device__ static int fix_env(int entry) { return entry; }
+  __device__ __forceinline__ static Draws draws(Env<T>& e, const Ids&, const T* host, uint64_t seed, uint32_t genv,
+                                                uint32_t episode) {
+    if (host) {
+      if (lane_id() < 12) e.vec3[lane_id()] = host[lane_id()];
+    } else {
+      bipedal_philox_draws(seed, genv, episode, e.vec3);
+    }
+    wsync();
+    return e.vec3;
+  }
+  __device__ __forceinline__ static void pose(const DevModel<T>& m, Env<T>& e, const Ids& ids, const Pipe&, int,
+                                              Draws draws) {
+    T d[12];
+    for (int j = 0; j < 12; j++) d[j] = draws[j];
+    wsync();
+    reset_env(m, e);
+    if (lane_id() == 0) {
+      e.qpos[ids.root_x] = d[0];
+      e.qpos[ids.root_y] = d[1];
+      e.qpos[ids.root_z] = (T)1.2;
+      for (int i = 0; i < 5; i++) {
+        e.qpos[ids.victim_x[i]] = e.qpos[ids.victim_x[i]] + d[2 + 2 * i];
+        e.qpos[ids.victim_y[i]] = e.qpos[ids.victim_y[i]] + d[3 + 2 * i];
+      }
+    }
+    wsync();
+  }
+  __device__ __forceinline__ static void finalize(const DevModel<T>& m, Env<T>& e, const Ids& ids, const Pipe& P, int bi) {
+    bipedal_obs(m, e, ids, 0, 0, 0, 1000.0, false, P.at<float>(P.o_bobs) + (size_t)bi * RK_OBS);
+    int l = lane_id();
+    if (l < 3) P.at<T>(P.o_bprev)[(size_t)bi * 6 + l] = e.xpos[3 * ids.torso + l];
+    wsync();
+  }
+  // the tracking reset of rescue_env.py:347-372 (the _prev_* / _fall_timer attributes survive,
+  // quirk B3) and prev_robot_pos
+  __device__ __forceinline__ static void track_reset(const DevModel<T>&, const Pipe& P, EnvT be, int env, int bi) {
+    const int l = lane_id();
+    if (l < 3) be.prev_robot_pos[3 * (size_t)env + l] = (double)P.at<T>(P.o_bprev)[(size_t)bi * 6 + l];
+    if (l == 0) {
+      be.step[env] = 0;
+      be.energy[env] = 1000.0;
+      be.energy_used[env] = 0.0;
+      if (be.energy_kind) be.energy_kind[env] = EK_PY;
+      be.rescued[env] = 0;
+      be.carried[env] = 0;
+      be.carrying[env] = 0;
+      be.closest[env] = __builtin_inf();
+      be.victims_rescued[env] = 0;
+      be.distance[env] = 0.0;
+      be.ttfr[env] = __builtin_nan("");
+      be.falls[env] = 0;
+      be.collisions[env] = 0;
     }
   }
-  wsync();
-  copy_g(P.at<T>(P.o_bq) + (size_t)bi * m.nq, e.qpos, m.nq);
-  if (l < m.nv) {
-    P.at<T>(P.o_bv)[(size_t)bi * m.nv + l] = 0;
-    P.at<T>(P.o_ba)[(size_t)bi * m.nv + l] = 0;
+  // the four stages' finisher (rk_step_end) stores the record, counts its settle steps and
+  // finalizes it after the tenth
+  template <int EPL, int LPS>
+  __device__ __forceinline__ static void settle_step(const DevModel<T>& Ms, const DevModel<T>& Mf, const Ids& ids,
+                                                     mgx_state s, EnvT be, const Pipe& P, char* smem, Env<T>&, int env,
+                                                     int bi, int slot, int maxit, T tol, T scale, bool) {
+    rk_settle_step(Ms, Mf, ids, s, be, P, smem, env, bi, slot, maxit, tol, scale);
   }
-  if (l == 0) {
-    P.at<T>(P.o_btime)[bi] = 0;
-    P.at<int>(P.o_bwarn)[bi] = 0;
-    P.at<int>(P.o_bep)[bi] = episode;
-    P.at<uint64_t>(P.o_bseed)[bi] = seed;
-    P.at<int>(P.o_bk)[bi] = 0;
-  }
-  wsync();
-}
-template <typename T>
-__device__ __forceinline__ void rk_bank_init(const DevModel<T>& m, Env<T>& e, const BipedalIds& ids, const Pipe& P,
-                                             int env, int bi, int episode, uint64_t seed, int env_offset) {
-  bipedal_philox_draws(seed, (uint32_t)(env_offset + env), (uint32_t)episode, e.vec3);
-  wsync();
-  rk_bank_init_draws(m, e, ids, P, bi, episode, seed, e.vec3);
-}
-
-// settle finished: the reset observation and prev_robot_pos (rescue_env.py:393-396)
-template <typename T>
-__device__ __forceinline__ void rk_bank_finalize(const DevModel<T>& m, Env<T>& e, const BipedalIds& ids, const Pipe& P,
-                                                 int bi) {
-  bipedal_obs(m, e, ids, 0, 0, 0, 1000.0, false, P.at<float>(P.o_bobs) + (size_t)bi * RK_OBS);
-  int l = lane_id();
-  if (l < 3) P.at<T>(P.o_bprev)[(size_t)bi * 6 + l] = e.xpos[3 * ids.torso + l];
-  wsync();
-}
-
-// the settled reset of record bi becomes env's live state for episode E: state, the tracking
-// reset of rescue_env.py:347-372 (the _prev_* / _fall_timer attributes survive, quirk B3), obs,
-// prev_robot_pos; episode E + 1
-template <typename T>
-__device__ __forceinline__ void rk_bank_copy_live(const DevModel<T>& m, const Pipe& P, mgx_state s, mgx_bipedal_env be,
-                                                  float* obs, int env, int bi, int E) {
-  int l = lane_id();
-  copy_g((T*)s.qpos + (size_t)env * m.nq, P.at<T>(P.o_bq) + (size_t)bi * m.nq, m.nq);
-  copy_g((T*)s.qvel + (size_t)env * m.nv, P.at<T>(P.o_bv) + (size_t)bi * m.nv, m.nv);
-  copy_g((T*)s.qacc_warmstart + (size_t)env * m.nv, P.at<T>(P.o_ba) + (size_t)bi * m.nv, m.nv);
-  for (int k = l; k < m.nv; k += 64) ((T*)s.qfrc_applied)[(size_t)env * m.nv + k] = 0;
-  for (int k = l; k < m.nu; k += 64) ((T*)s.ctrl)[(size_t)env * m.nu + k] = 0;
-  for (int k = l; k < 6 * m.nbody; k += 64) ((T*)s.xfrc_applied)[(size_t)env * 6 * m.nbody + k] = 0;
-  copy_g(obs + (size_t)env * RK_OBS, P.at<float>(P.o_bobs) + (size_t)bi * RK_OBS, RK_OBS);
-  if (l < 3) be.prev_robot_pos[3 * (size_t)env + l] = (double)P.at<T>(P.o_bprev)[(size_t)bi * 6 + l];
-  if (l == 0) {
-    ((T*)s.time)[env] = P.at<T>(P.o_btime)[bi];
-    if (s.warning) s.warning[env] += P.at<int>(P.o_bwarn)[bi];
-    be.step[env] = 0;
-    be.energy[env] = 1000.0;
-    be.energy_used[env] = 0.0;
-    if (be.energy_kind) be.energy_kind[env] = EK_PY;
-    be.rescued[env] = 0;
-    be.carried[env] = 0;
-    be.carrying[env] = 0;
-    be.closest[env] = __builtin_inf();
-    be.victims_rescued[env] = 0;
-    be.distance[env] = 0.0;
-    be.ttfr[env] = __builtin_nan("");
-    be.falls[env] = 0;
-    be.collisions[env] = 0;
-    if (be.episode) be.episode[env] = E + 1;
-  }
-  wsync();
-}
+};
 
 // ---------------------------------------------------------------- stage pieces
 // R(k) body: the slot's stage state into the row builder's Env, then forward up to the rows.
@@ -228,7 +217,7 @@ __device__ __forceinline__ void rk_step_end(const DevModel<T>& m, Env<T>& f, con
     bank_store_state(m, f, P, bi, warn);
     wsync();
     const int k = P.at<int>(P.o_bk)[bi] + 1;
-    if (k == 10) rk_bank_finalize(m, f, ids, P, bi);
+    if (k == 10) BipedalBank<T>::finalize(m, f, ids, P, bi);
     if (l == 0) P.at<int>(P.o_bk)[bi] = k;
     wsync();
     return;
@@ -251,19 +240,7 @@ __device__ __forceinline__ void rk_step_end(const DevModel<T>& m, Env<T>& f, con
     for (int i = l; i < RK_OBS; i += 64) final_obs[(size_t)env * RK_OBS + i] = obs[(size_t)env * RK_OBS + i];
   __threadfence();
   wsync();
-  const int E = be.episode[env];
-  bool ready = false;
-  int bi2 = 0;
-  if (P.R > 0) {
-    bi2 = env * P.R + E % P.R;
-    ready = P.at<int>(P.o_bk)[bi2] == 10 && P.at<int>(P.o_bep)[bi2] == E && P.at<uint64_t>(P.o_bseed)[bi2] == seed;
-  }
-  if (ready) {
-    rk_bank_copy_live(m, P, s, be, obs, env, bi2, E);
-    rk_bank_init(m, f, ids, P, env, bi2, E + P.R, seed, env_offset);
-  } else if (l == 0) {
-    P.at<int>(P.o_fix)[atomicAdd(P.ctr() + 5, 1)] = env;
-  }
+  bank_install_or_list<BipedalBank<T>>(m, f, ids, P, s, be, obs, seed, env_offset, true, env);
 }
 
 // F(k) body for one active slot (Env f: the finisher layout). Returns true when the slot's
@@ -458,63 +435,16 @@ __device__ __forceinline__ void rk_settle_step(const DevModel<T>& Ms, const DevM
   }
 }
 
-// Restart record bi for `episode` (host draws [12] or Philox) and settle it: 10 RK4 mj_steps
-// (rescue_env.py:390-391); the record ends finalized with bk = 10.
-template <typename T>
-__device__ __forceinline__ void rk_settle_reset(const DevModel<T>& Ms, const DevModel<T>& Mf, const BipedalIds& ids,
-                                                mgx_state s, mgx_bipedal_env be, const Pipe& P, char* smem,
-                                                int env, int bi, int episode, const T* draws, uint64_t seed,
-                                                int env_offset, int maxit, T tol, T scale) {
-  {
-    Env<T> e;
-    env_bind(Ms, e, smem);
-    bind_carry_tail(Ms, e, P, env);
-    if (draws) {
-      if (lane_id() < 12) e.vec3[lane_id()] = draws[lane_id()];
-    } else {
-      bipedal_philox_draws(seed, (uint32_t)(env_offset + env), (uint32_t)episode, e.vec3);
-    }
-    wsync();
-    rk_bank_init_draws(Ms, e, ids, P, bi, episode, seed, e.vec3);
-  }
-  __threadfence();
-  __syncthreads();
-  for (int t = 0; t < 10; t++) rk_settle_step(Ms, Mf, ids, s, be, P, smem, env, bi, env, maxit, tol, scale);
-}
-
-// reset() of a staged batch (RK_SETTLE_RESET, one workgroup per env; with Philox draws and banks
-// it also prefills the env's R banks) and the step's resets whose bank was not ready
-// (RK_SETTLE_FIXUP, grid-stride over the finisher's list).
+// reset() of a staged batch and the step's resets whose bank was not ready: the bank layer's settle
+// (mgx_bank.h) over this translation unit's stages
 template <typename T>
 __global__ void __launch_bounds__(64) k_rk_settle(DevModel<T> Ms, DevModel<T> Mf, BipedalIds ids, mgx_state s,
                                                   mgx_bipedal_env be, const T* draws, float* obs, uint64_t seed,
                                                   int env_offset, int n_env, const uint8_t* mask, Pipe P, int mode,
                                                   int maxit, T tol, T scale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int cnt = mode == RK_SETTLE_FIXUP ? P.ctr()[5] : n_env;
-  for (int i = blockIdx.x; i < cnt; i += gridDim.x) {
-    const int env = mode == RK_SETTLE_FIXUP ? P.at<int>(P.o_fix)[i] : i;
-    if (mode == RK_SETTLE_RESET && mask && !mask[env]) continue;
-    const int E = be.episode ? be.episode[env] : 0;
-    const int bi = P.R > 0 ? env * P.R + E % P.R : env;
-    const T* d = draws ? draws + (size_t)env * 12 : nullptr;
-    rk_settle_reset(Ms, Mf, ids, s, be, P, smem, env, bi, E, d, seed, env_offset, maxit, tol, scale);
-    rk_bank_copy_live(Mf, P, s, be, obs, env, bi, E);
-    if (P.R > 0 && mode == RK_SETTLE_FIXUP) {
-      Env<T> e;
-      env_bind(Ms, e, smem);
-      bind_carry_tail(Ms, e, P, env);
-      rk_bank_init(Ms, e, ids, P, env, bi, E + P.R, seed, env_offset);
-    } else if (P.R > 0 && !draws) {
-      for (int k = 1; k <= P.R; k++)
-        rk_settle_reset(Ms, Mf, ids, s, be, P, smem, env, env * P.R + (E + k) % P.R, E + k, (const T*)nullptr, seed,
-                        env_offset, maxit, tol, scale);
-    } else if (lane_id() == 0) {
-      P.at<int>(P.o_bk)[bi] = -1;  // a scratch record: nothing to settle
-    }
-    __threadfence();
-    __syncthreads();
-  }
+  bank_settle<BipedalBank<T>, T, RK_EPL, RK_LPS>(Ms, Mf, ids, s, be, draws, obs, seed, env_offset, n_env, mask, P, mode,
+                                                 maxit, tol, scale, smem);
 }
 
 // mj_checkAcc's outcome: mj_resetData, mj_forward, RK4 (monolithic layout, rows in the pipe's
@@ -524,23 +454,10 @@ __global__ void __launch_bounds__(64) k_rk_template(DevModel<T> m, Pipe P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Env<T> e;
   env_bind<T, GB>(m, e, smem, GB ? P.at<T>(P.o_tscr) : nullptr);
-  const int l = lane_id();
   reset_env(m, e);
   forward<T>(m, e);
   rk4<T>(m, e);
-  for (int k = l; k < m.nq; k += 64) P.at<T>(P.o_tq)[k] = e.qpos[k];
-  for (int k = l; k < m.nv; k += 64) P.at<T>(P.o_tv)[k] = e.qvel[k];
-  if (l < m.nv) P.at<T>(P.o_ta)[l] = e.qacc_ws;
-  for (int k = l; k < 3 * m.nbody; k += 64) { P.at<T>(P.o_tx)[k] = e.xpos[k]; P.at<T>(P.o_tsc)[k] = e.subtree_com[k]; }
-  for (int k = l; k < 4 * m.nbody; k += 64) P.at<T>(P.o_txq)[k] = e.xquat[k];
-  const int nc = e.ncon < P.maxC ? e.ncon : P.maxC;
-  for (int k = l; k < nc; k += 64) {
-    P.at<int>(P.o_tcg)[2 * k] = e.con_geom[2 * k];
-    P.at<int>(P.o_tcg)[2 * k + 1] = e.con_geom[2 * k + 1];
-    P.at<T>(P.o_tcd)[k] = e.con_dist[k];
-    P.at<T>(P.o_tcm)[k] = e.con_mu[k];
-  }
-  if (l == 0) { P.at<int>(P.o_tn)[0] = nc; P.at<T>(P.o_tt)[0] = e.time; }
+  template_store(m, e, P);
 }
 
 }  // namespace mgx
@@ -548,38 +465,12 @@ __global__ void __launch_bounds__(64) k_rk_template(DevModel<T> m, Pipe P) {
 // ------------------------------------------------------------------------- host side
 namespace {
 
-int fail(int code, const std::string& msg) { return host_fail(code, msg); }
+int settle_lds(const mgx_model* m, const Pipe& P) { return staged_settle_lds(m, P, RK_LPS, 1, 4); }
 
-struct RkSide {
-  hipStream_t s;
-  hipEvent_t rows, big;
-};
-RkSide* rk_side(hipStream_t st) {
-  static std::mutex mu;
-  static std::map<std::pair<hipStream_t, int>, RkSide*> cache;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  auto key = std::make_pair(st, dev);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  RkSide* x = new RkSide{};
-  if (hipStreamCreateWithFlags(&x->s, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&x->rows, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&x->big, hipEventDisableTiming) != hipSuccess) {
-    delete x;
-    x = nullptr;
-  }
-  cache[key] = x;
-  return x;
-}
-
-int settle_lds(const mgx_model* m, const Pipe& P) {
-  int b = staged_pgs_lds_bytes(m, P.maxE, RK_LPS, 1, 4);
-  if (m->Ls.bytes > b) b = m->Ls.bytes;
-  if (m->Lf.bytes > b) b = m->Lf.bytes;
-  return b;
-}
+const StagedTask kBipedalStaged = {"bipedal", [](const mgx_model* m) { return m->staged_rk_ok; },
+                                   "staged RK4 step: model outside the staged pipeline's range", true, true, RK_OBS, 0,
+                                   {k_rk_template<float, false>, k_rk_template<float, true>},
+                                   {k_rk_template<double, false>, k_rk_template<double, true>}};
 
 template <typename T>
 void launch_rk_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big) {
@@ -596,13 +487,12 @@ int step_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms,
                 int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
   const int banks = autoreset ? e->banks : 0;
-  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, true, RK_OBS);
-  if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_bipedal_workspace_bytes");
+  if (int rc = task_pipe_checked(kBipedalStaged, m, e->workspace, e->workspace_bytes, n_env, e->banks, &P)) return rc;
   const int slots = n_env * (1 + banks);
-  const T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+  const T scale = staged_scale(M);
   const int mlds = staged_pgs_lds_bytes(m, P.capE, RK_LPS, 1, 4), wlds = staged_pgs_lds_bytes(m, P.maxE, RK_LPS, 1, 4);
   const int wgrid = 64 / RK_LPS * MGX_PGS_WIDE_GRID;
-  RkSide* side = m->hooks.side_stream ? rk_side(st) : nullptr;
+  SideStream* side = m->hooks.side_stream ? side_stream(st) : nullptr;
   for (int k = 0; k < 4; k++) {
     hipLaunchKernelGGL(k_rk_rows<T>, dim3(slots), dim3(64), m->Ls.bytes, st, Ms, m->bp, *s, *e, action, n_env, mask, P,
                        banks, k);
@@ -623,9 +513,8 @@ int step_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms,
     hipLaunchKernelGGL(k_rk_finish<T>, dim3(n_env), dim3(64), m->Lf.bytes, st, Mf, m->bp, *s, *e, action, obs, reward,
                        terminated, truncated, final_obs, autoreset, seed, env_offset, n_env, mask, P, banks, k, 0);
   }
-  const int fgrid = n_env < 256 ? n_env : 256;
-  hipLaunchKernelGGL(k_rk_settle<T>, dim3(fgrid), dim3(64), settle_lds(m, P), st, Ms, Mf, m->bp, *s, *e,
-                     (const T*)nullptr, obs, seed, env_offset, n_env, (const uint8_t*)nullptr, P, (int)RK_SETTLE_FIXUP,
+  hipLaunchKernelGGL(k_rk_settle<T>, dim3(fixup_grid(n_env)), dim3(64), settle_lds(m, P), st, Ms, Mf, m->bp, *s, *e,
+                     (const T*)nullptr, obs, seed, env_offset, n_env, (const uint8_t*)nullptr, P, (int)SETTLE_FIXUP,
                      M.iterations, M.tolerance, scale);
   MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
@@ -636,11 +525,10 @@ int reset_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms
                  const mgx_state* s, const mgx_bipedal_env* e, const T* draws, float* obs, uint64_t seed, int env_offset,
                  int n_env, const uint8_t* mask, hipStream_t st) {
   Pipe P;
-  const size_t need = make_staged_pipe(m, e->workspace, n_env, e->banks, &P, true, RK_OBS);
-  if (e->workspace_bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_bipedal_workspace_bytes");
-  const T scale = (T)1 / (M.meaninertia * (T)(M.nv > 1 ? M.nv : 1));
+  if (int rc = task_pipe_checked(kBipedalStaged, m, e->workspace, e->workspace_bytes, n_env, e->banks, &P)) return rc;
+  const T scale = staged_scale(M);
   hipLaunchKernelGGL(k_rk_settle<T>, dim3(n_env), dim3(64), settle_lds(m, P), st, Ms, Mf, m->bp, *s, *e, draws, obs, seed,
-                     env_offset, n_env, mask, P, (int)RK_SETTLE_RESET, M.iterations, M.tolerance, scale);
+                     env_offset, n_env, mask, P, (int)SETTLE_RESET, M.iterations, M.tolerance, scale);
   MGX_HIPCHK(hipGetLastError());
   return MGX_OK;
 }
@@ -648,9 +536,9 @@ int reset_staged(const mgx_model* m, const DevModel<T>& M, const DevModel<T>& Ms
 template <typename T>
 int configure_t(const mgx_model* m) {
   Pipe P;
-  make_staged_pipe(m, nullptr, 1, 1, &P, true, RK_OBS);
+  task_pipe(kBipedalStaged, m, nullptr, 1, 1, &P);
   const int wl = staged_pgs_lds_bytes(m, P.maxE, RK_LPS, 1, 4);
-  if (wl > 160 * 1024) return fail(MGX_E_CAPACITY, "staged RK4 solver LDS exceeds 160 KiB");
+  if (wl > 160 * 1024) return host_fail(MGX_E_CAPACITY, "staged RK4 solver LDS exceeds 160 KiB");
   return mgx_set_lds(k_rk_rows<T>, m->Ls.bytes) | mgx_set_lds(k_rk_finish<T>, m->Lf.bytes) |
          mgx_set_lds(k_rk_settle<T>, settle_lds(m, P)) | mgx_set_lds(k_rk_template<T, true>, m->L.bytes) |
          mgx_set_lds(k_rk_template<T, false>, m->L.bytes) |
@@ -668,8 +556,7 @@ int bipedal_staged_configure(const mgx_model* m) {
 int bipedal_step_staged(const mgx_model* m, const mgx_state* s, const mgx_bipedal_env* e, const float* action, float* obs,
                         double* reward, uint8_t* terminated, uint8_t* truncated, float* final_obs, int autoreset,
                         uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
-  if (!m->staged_rk_ok) return fail(MGX_E_UNSUPPORTED, "staged RK4 step: model outside the staged pipeline's range");
-  if (e->banks < 0 || e->banks > 16) return fail(MGX_E_ARG, "banks must be in [0, 16]");
+  if (int rc = staged_check(kBipedalStaged, m, e->banks)) return rc;
   if (m->precision == MGX_F32)
     return step_staged<float>(m, m->mf, m->mfs, m->mff, s, e, action, obs, reward, terminated, truncated, final_obs,
                               autoreset, seed, env_offset, n_env, mask, st);
@@ -679,8 +566,7 @@ int bipedal_step_staged(const mgx_model* m, const mgx_state* s, const mgx_bipeda
 
 int bipedal_reset_staged(const mgx_model* m, const mgx_state* s, const mgx_bipedal_env* e, const void* draws,
                          float* obs, uint64_t seed, int env_offset, int n_env, const uint8_t* mask, hipStream_t st) {
-  if (!m->staged_rk_ok) return fail(MGX_E_UNSUPPORTED, "staged RK4 step: model outside the staged pipeline's range");
-  if (e->banks < 0 || e->banks > 16) return fail(MGX_E_ARG, "banks must be in [0, 16]");
+  if (int rc = staged_check(kBipedalStaged, m, e->banks)) return rc;
   if (m->precision == MGX_F32)
     return reset_staged<float>(m, m->mf, m->mfs, m->mff, s, e, (const float*)draws, obs, seed, env_offset, n_env, mask,
                                st);
@@ -689,38 +575,20 @@ int bipedal_reset_staged(const mgx_model* m, const mgx_state* s, const mgx_biped
 }
 
 int64_t bipedal_workspace_bytes(const mgx_model* m, int n_env, int banks) {
-  if (!m || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_rk_ok) return fail(MGX_E_UNSUPPORTED, "staged RK4 step: model outside the staged pipeline's range");
-  return (int64_t)make_staged_pipe(m, nullptr, n_env, banks, nullptr, true, RK_OBS);
+  return staged_workspace_bytes(kBipedalStaged, m, n_env, banks);
 }
 
 int bipedal_workspace_init(const mgx_model* m, void* workspace, uint64_t bytes, int n_env, int banks, hipStream_t st) {
-  if (!m || !workspace || n_env <= 0 || banks < 0 || banks > 16) return fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_rk_ok) return fail(MGX_E_UNSUPPORTED, "staged RK4 step: model outside the staged pipeline's range");
-  Pipe P;
-  const size_t need = make_staged_pipe(m, workspace, n_env, banks, &P, true, RK_OBS);
-  if (bytes < need) return fail(MGX_E_ARG, "workspace smaller than mgx_bipedal_workspace_bytes");
-  MGX_HIPCHK(hipMemsetAsync(workspace, 0, need, st));
-  const size_t nb = (size_t)n_env * (banks > 0 ? banks : 1);
-  MGX_HIPCHK(hipMemsetAsync(P.base + P.o_bk, 0xFF, nb * 4, st));  // bank settle counters = -1 (empty)
-  if (m->precision == MGX_F32) {
-    if (m->L.gB) hipLaunchKernelGGL((k_rk_template<float, true>), dim3(1), dim3(64), m->L.bytes, st, m->mf, P);
-    else hipLaunchKernelGGL((k_rk_template<float, false>), dim3(1), dim3(64), m->L.bytes, st, m->mf, P);
-  } else {
-    if (m->L.gB) hipLaunchKernelGGL((k_rk_template<double, true>), dim3(1), dim3(64), m->L.bytes, st, m->md, P);
-    else hipLaunchKernelGGL((k_rk_template<double, false>), dim3(1), dim3(64), m->L.bytes, st, m->md, P);
-  }
-  MGX_HIPCHK(hipGetLastError());
-  return MGX_OK;
+  return staged_workspace_init(kBipedalStaged, m, workspace, bytes, n_env, banks, st);
 }
 }  // namespace mgx
 
 extern "C" {
 int mgx_bipedal_workspace_layout(const mgx_model* m, int n_env, int banks, int64_t* out, int n_out) {
-  if (!m || !out || n_env <= 0 || banks < 0 || banks > 16 || n_out < 6) return fail(MGX_E_ARG, "bad argument");
-  if (!m->staged_rk_ok) return fail(MGX_E_UNSUPPORTED, "staged RK4 step: model outside the staged pipeline's range");
+  if (!m || !out || n_env <= 0 || banks < 0 || banks > 16 || n_out < 6) return host_fail(MGX_E_ARG, "bad argument");
+  if (!m->staged_rk_ok) return host_fail(MGX_E_UNSUPPORTED, kBipedalStaged.refusal);
   Pipe P;
-  make_staged_pipe(m, nullptr, n_env, banks, &P, true, RK_OBS);
+  task_pipe(kBipedalStaged, m, nullptr, n_env, banks, &P);
   const int64_t v[12] = {(int64_t)P.o_rk, P.rk_stride, (int64_t)P.o_rks, (int64_t)P.o_ne, P.S,
                          m->precision == MGX_F32 ? 4 : 8, (int64_t)P.o_scal, P.maxE, (int64_t)P.o_niter,
                          (int64_t)P.o_B, P.bcap, (int64_t)P.o_blk};

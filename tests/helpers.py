@@ -34,6 +34,59 @@ def load_states(batch, states):
         t.copy_(torch.from_numpy(arr).to(t.dtype))
 
 
+def masked_step(env, act, mask=None):
+    """TaskVectorEnv.step with an env mask (the C entry point's argument, which step() leaves out)."""
+    import ctypes as C
+    from mujoco_gymnasium_environments_amd.batch import _ptr
+    from mujoco_gymnasium_environments_amd.native import check
+    env._env.action_f64 = 0
+    check(env._step_fn(env.native.handle, C.byref(env.batch.state), C.byref(env._env), _ptr(act), _ptr(env.obs),
+                       _ptr(env.reward), _ptr(env.terminated), _ptr(env.truncated),
+                       _ptr(env.final_obs) if env.autoreset else None, 1 if env.autoreset else 0, env.seed_value,
+                       env.env_offset, env.num_envs, _ptr(mask), None), env._step_name)
+
+
+def reset_and_masked_step_run(env, nu, scale, steps=12, reset_at=5, masked_at=8):
+    """reset(), then `steps` steps under fixed uniform actions, with a reset of envs {1, 3} before
+    step `reset_at` and step `masked_at` taken by envs {0, 3} only. Returns, as bytes (NaNs and signed
+    zeros count), every output after every step and every tensor of the env and its physics batch
+    at the end, and the number of episodes that ended."""
+    import torch
+    n = env.num_envs
+    idx = torch.arange(n, device=env.device)
+    reset_mask = ((idx == 1) | (idx == 3)).to(torch.uint8)
+    step_mask = ((idx == 0) | (idx == 3)).to(torch.uint8)
+    g = torch.Generator(device=env.device)
+    g.manual_seed(5)
+    env.reset()
+    out, ends = [], 0
+    for t in range(steps):
+        a = ((torch.rand(n, nu, device=env.device, generator=g) * 2 - 1) * scale).float().contiguous()
+        if t == reset_at:
+            env.reset(env_mask=reset_mask)
+        masked_step(env, a, step_mask if t == masked_at else None)
+        torch.cuda.synchronize()
+        out.append({k: getattr(env, k).cpu().numpy().tobytes()
+                    for k in ("obs", "reward", "terminated", "truncated", "final_obs")})
+        ends += int((env.terminated | env.truncated).sum())
+    end = {}
+    for owner, skip in ((env, ("workspace",)), (env.batch, ("scratch",))):
+        for k, v in vars(owner).items():
+            if isinstance(v, torch.Tensor) and k not in skip:
+                end[f"{type(owner).__name__}.{k}"] = v.cpu().numpy().tobytes()
+    return out, end, ends
+
+
+def assert_runs_bit_equal(ref, got):
+    for t, (x, y) in enumerate(zip(ref[0], got[0])):
+        for k in x:
+            assert x[k] == y[k], f"step {t}: {k} differs"
+    assert ref[1].keys() == got[1].keys()
+    for k in ref[1]:
+        assert ref[1][k] == got[1][k], f"final {k} differs"
+    assert ref[2] == got[2]
+
+
 def oracle_at(packed, state):
     from oracle.mjref import RefSim
     s = RefSim(packed)

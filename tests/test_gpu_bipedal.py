@@ -328,6 +328,21 @@ def test_bipedal_bank_count_does_not_change_trajectories(banks):
     assert w0 == w1
 
 
+def test_bipedal_reset_and_masked_step_mid_run():
+    """A masked reset() and a masked step in the middle of a run with 3-step episodes, banks = 2
+    against banks = 0: the settle kernel's reset mode under a mask, its bank prefill, the ready-bank
+    install (an env's first two autoresets) and the fixup list (its third: the bank restarted six
+    steps earlier needs ten to settle) all give the same bits, and masked envs stay put. Every
+    output of every step and every state tensor at the end is compared bytewise."""
+    from mujoco_gymnasium_environments_amd.envs.bipedal import BipedalVectorEnv
+    from tests.helpers import assert_runs_bit_equal, reset_and_masked_step_run
+    runs = [reset_and_masked_step_run(
+        BipedalVectorEnv(4, precision="f64", seed=9, max_episode_steps=3, staged=True, banks=b), 26, 100.0)
+        for b in (0, 2)]
+    assert runs[0][2] >= 12
+    assert_runs_bit_equal(*runs)
+
+
 def _obs_close(x, y, tol=1e-6):
     """Within tol absolute plus tol relative: the observation is float32, whose rounding of an
     entry near 30 (positions, distances) moves by 2-4e-6 when its fp64 source moves by 1e-12."""

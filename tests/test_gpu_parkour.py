@@ -213,6 +213,21 @@ def test_parkour_bank_count_does_not_change_trajectories(banks):
     assert w0 == w1
 
 
+def test_parkour_reset_and_masked_step_mid_run():
+    """A masked reset() and a masked step in the middle of a run with 3-step episodes, banks = 2
+    against banks = 0: the settle kernel's reset mode under a mask, its bank prefill, the fixup list
+    and the ready-bank install all give the same bits, and masked envs stay put. Every output of
+    every step and every state tensor at the end is compared bytewise."""
+    from mujoco_gymnasium_environments_amd.envs.parkour import ParkourVectorEnv, action_limits
+    from tests.helpers import assert_runs_bit_equal, reset_and_masked_step_run
+    lim = torch.as_tensor(action_limits(), dtype=torch.float32, device="cuda:0")
+    runs = [reset_and_masked_step_run(
+        ParkourVectorEnv(4, precision="f64", seed=9, max_episode_steps=3, staged=True, banks=b), 16, lim)
+        for b in (0, 2)]
+    assert runs[0][2] >= 8
+    assert_runs_bit_equal(*runs)
+
+
 def test_parkour_end_to_end_f64_bench_actions(parkour_model):
     """Bench conditions (BASELINE configs[1]): U(-lim, lim) actions over the full action space, the
     staged fp64 step of 8 envs x 25 steps against the oracle for as long as the oracle determines the

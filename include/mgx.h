@@ -993,6 +993,107 @@ int64_t mgx_rollout_bytes(const mgx_model *m, int slots, int with_sensors);
 int mgx_rollout(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io, int n_env,
                 const uint8_t *env_mask, void *stream);
 
+/* ---- RGB camera images (ray-traced rgb_array) -------------------------------------------------- */
+/* The colour image of one of the model's cameras for every env, on the primary rays of
+ * mgx_ray_camera. This is NOT MuJoCo's OpenGL image: it is the small shading model stated here
+ * (an own design on MuJoCo's light and material parameters; tests/render_reference.py is its numpy
+ * float64 restatement). Intersections run in the model's real type, shading from the hit point on
+ * in float32.
+ *
+ * Primary ray: pixel (r, c)'s ray p + x v of mgx_ray_camera; d = v / |v|.
+ * Miss: the background. Skybox texture builtin gradient: rgb2 + (rgb1 - rgb2) (1/2 + d_z / 2);
+ *   builtin flat: rgb1; any other or no skybox: black.
+ * Hit of geom g at x, P = p + x v. n is the outward unit normal of the surface PIECE whose root
+ *   won inside the intersection routine (recorded there, never re-derived from P), in the geom
+ *   frame, rotated to world: plane +z; sphere radial; capsule radial on the side, from the cap
+ *   centre on a cap; cylinder radial on the side, +-z on a cap; box +-e_i. Ties go to the first
+ *   piece in the routine's order (side, -z cap, +z cap; faces -x +x -y +y -z +z). n <- -n when
+ *   n.v > 0 (the ray started inside the geom).
+ * Base colour c = rgb(geom_rgba) * tex; tex = 1 without a texture; rgb1 for builtin flat; builtin
+ *   checker on a PLANE geom: with the hit's plane-local coordinates (u, w) and cell edges L_k,
+ *   rgb1 when floor(u / L_0) + floor(w / L_1) is even, else rgb2, L_k = size_k / texrepeat_k where
+ *   size_k > 0 and not texuniform, otherwise 1 / (2 texrepeat_k); the mean of rgb1 and rgb2 for
+ *   any other builtin texture on any other geom (a documented simplification).
+ * Lights: the headlight (if active; directional along the camera's view axis, L = the camera's +Z,
+ *   no shadow) and the active model lights. Directional: L = -dir, att = spot = 1. Positional: L
+ *   points from P to the light at distance l, att = 1 / (a0 + a1 l + a2 l^2); cos t = -L.dir;
+ *   spot = 0 when t > cutoff, else max(0, cos t)^exponent; a cutoff >= 180 degrees means no cone
+ *   (spot = 1).
+ * Blinn-Phong per channel, A the sum of the lights' ambient terms, H = normalize(L - d), k_s, s, e
+ *   the material's specular, shininess, emission (0.5, 0.5, 0 without a material):
+ *   C = e c + c A + sum_l vis_l att_l spot_l [c diffuse_l max(0, n.L)
+ *                                             + k_s specular_l max(0, n.H)^(128 s) [n.L > 0]]
+ * Shadows: vis_l = 0 when the light casts shadows and the ray from P + eps n along L meets an
+ *   enabled geom of alpha exactly 1, within l for a positional light, at any distance for a
+ *   directional one; eps = 1e-4 max(1, |P - camera position|). Shadow rays use the call's enabled
+ *   set; planes are hit from the front only.
+ * Translucency: a hit with alpha a < 1 gives a C + (1 - a) (colour of the same ray restarted at P
+ *   with that geom skipped), resolved front to back over at most MGX_RENDER_MAX_LAYERS hits; the
+ *   last one counts as opaque. Geoms eliminated by mgx_ray_configure stay eliminated.
+ * Output: rgbf = clamp(C, 0, 1), rgb8 = (uint8)(rgbf 255 + 0.5).
+ * Not provided: reflectance, haze / fog, anti-aliasing, sites and decor, cube-texture detail,
+ * textured non-plane geoms, meshes / hfields / ellipsoids, textures from files. */
+#define MGX_RENDER_MAX_LAYERS 4
+#define MGX_RENDER_MAX_LIGHT 8
+#define MGX_TEX_2D 0
+#define MGX_TEX_CUBE 1
+#define MGX_TEX_SKYBOX 2
+#define MGX_BUILTIN_NONE 0
+#define MGX_BUILTIN_GRADIENT 1
+#define MGX_BUILTIN_CHECKER 2
+#define MGX_BUILTIN_FLAT 3
+
+/* Host tables (the Python MJCF compiler's appearance fields); copied by mgx_render_configure. */
+typedef struct mgx_render_desc {
+  int32_t ngeom, nmat, ntex, nlight;   /* ngeom must equal the model's; nlight <= MGX_RENDER_MAX_LIGHT */
+  const double *geom_rgba;             /* [ngeom][4] the effective colour (geom_rgba_eff) */
+  const int32_t *geom_matid;           /* [ngeom] material or -1 */
+  const double *mat_emission, *mat_specular, *mat_shininess;   /* [nmat] */
+  const int32_t *mat_texid;            /* [nmat] texture or -1 */
+  const double *mat_texrepeat;         /* [nmat][2] */
+  const int32_t *mat_texuniform;       /* [nmat] */
+  const int32_t *tex_type;             /* [ntex] MGX_TEX_* */
+  const int32_t *tex_builtin;          /* [ntex] MGX_BUILTIN_* */
+  const int32_t *tex_file;             /* [ntex] != 0: the texture comes from a file (refused where used) */
+  const double *tex_rgb1, *tex_rgb2;   /* [ntex][3] */
+  const int32_t *light_bodyid;         /* [nlight] */
+  const int32_t *light_mode;           /* [nlight] MGX_CAM_FIXED only */
+  const int32_t *light_directional, *light_castshadow, *light_active;   /* [nlight] */
+  const double *light_pos, *light_dir; /* [nlight][3] body frame, dir normalised */
+  const double *light_ambient, *light_diffuse, *light_specular, *light_attenuation;   /* [nlight][3] */
+  const double *light_cutoff;          /* [nlight] degrees */
+  const double *light_exponent;        /* [nlight] */
+  int32_t headlight_active;
+  int32_t skybox_tex;                  /* the model's skybox texture or -1 */
+  double headlight_ambient[3], headlight_diffuse[3], headlight_specular[3];
+} mgx_render_desc;
+
+/* Needs a prior mgx_ray_configure and refuses what that refuses. MGX_E_UNSUPPORTED, with a message
+ * that names the cause, for a file texture on a material that a geom uses and for a light whose
+ * mode is not fixed; MGX_E_CAPACITY for more than MGX_RENDER_MAX_LIGHT lights or a model whose
+ * staged scene exceeds 64 KiB of LDS. A later mgx_ray_configure drops the render tables. */
+int mgx_render_configure(mgx_model *m, const mgx_render_desc *desc);
+
+/* The render scene: per env the ray scene of mgx_ray_scene (same layout, at the front) followed by
+ * each light's world position [3] and direction [3]: body frame o (light_pos, light_dir), so a
+ * light on a moving body moves with it. One kernel, sharing mgx_ray_scene's code, writes every byte
+ * of a selected env's scene. */
+int64_t mgx_render_scene_bytes(const mgx_model *m, int n_env);
+int mgx_render_scene(const mgx_model *m, const mgx_state *state, void *scene, uint64_t bytes, int n_env,
+                     const uint8_t *env_mask, void *stream);
+
+/* rgb8 uint8 [N][H][W][3]; rgbf float32 [N][H][W][3], the same colour before quantisation; depth
+ * and seg those of mgx_ray_camera (the first hit). Each output is nullable, at least one must be
+ * given. geom_enable, bodyexclude and env_mask as in mgx_ray_camera. Asynchronous on the stream, no
+ * allocation or synchronisation; rows of deselected envs untouched, every byte of a selected env's
+ * non-NULL outputs written; no atomics, so results are bit-reproducible.
+ * `scene` must be a buffer written by mgx_render_scene for at least n_env envs: the call takes no
+ * size and cannot check it. A buffer of mgx_ray_scene will not do: the render scene is longer per
+ * env (the lights) and so has another stride, and the kernel would read past each env's scene. */
+int mgx_render_camera(const mgx_model *m, const void *scene, int cam, int height, int width,
+                      const uint8_t *geom_enable, int bodyexclude, uint8_t *rgb8, float *rgbf, float *depth,
+                      int32_t *seg, int n_env, const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

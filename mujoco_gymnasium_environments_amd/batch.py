@@ -16,6 +16,7 @@ from . import cabi, mjcf
 from .native import MGX_F32, MGX_F64, check, lib
 from .dynamics import DynamicsMethods
 from .rays import RayMethods
+from .render import RenderMethods
 from .sensors import SensorMethods
 from .rollouts import RolloutMethods
 from .transitions import TransitionMethods
@@ -61,7 +62,7 @@ class NativeModel:
             self.handle = None
 
 
-class PhysicsBatch(RayMethods, SensorMethods, DynamicsMethods, TransitionMethods, RolloutMethods):
+class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, TransitionMethods, RolloutMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

@@ -325,6 +325,59 @@ class MgxRolloutIO(C.Structure):
                 ("workspace_bytes", C.c_uint64)]
 
 
+MGX_RENDER_MAX_LAYERS, MGX_RENDER_MAX_LIGHT = 4, 8  # include/mgx.h
+MGX_TEX_2D, MGX_TEX_CUBE, MGX_TEX_SKYBOX = 0, 1, 2  # mjcf.TEX_TYPES
+MGX_BUILTIN_NONE, MGX_BUILTIN_GRADIENT, MGX_BUILTIN_CHECKER, MGX_BUILTIN_FLAT = 0, 1, 2, 3  # mjcf.TEX_BUILTIN
+
+# (field, kind) of mgx_render_desc's tables in declaration order; each is the Model array of that
+# name except geom_rgba, which is Model.geom_rgba_eff
+_RENDER_ARRAYS = [
+    ("geom_rgba", "d"), ("geom_matid", "i"), ("mat_emission", "d"), ("mat_specular", "d"), ("mat_shininess", "d"),
+    ("mat_texid", "i"), ("mat_texrepeat", "d"), ("mat_texuniform", "i"), ("tex_type", "i"), ("tex_builtin", "i"),
+    ("tex_file", "i"), ("tex_rgb1", "d"), ("tex_rgb2", "d"), ("light_bodyid", "i"), ("light_mode", "i"),
+    ("light_directional", "i"), ("light_castshadow", "i"), ("light_active", "i"), ("light_pos", "d"),
+    ("light_dir", "d"), ("light_ambient", "d"), ("light_diffuse", "d"), ("light_specular", "d"),
+    ("light_attenuation", "d"), ("light_cutoff", "d"), ("light_exponent", "d"),
+]
+
+
+class MgxRenderDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("ngeom", "nmat", "ntex", "nlight")] +
+                [(n, _PTR[k]) for n, k in _RENDER_ARRAYS] +
+                [("headlight_active", C.c_int32), ("skybox_tex", C.c_int32), ("headlight_ambient", C.c_double * 3),
+                 ("headlight_diffuse", C.c_double * 3), ("headlight_specular", C.c_double * 3)])
+
+
+def skybox_texture(model: Model) -> int:
+    """The model's skybox: its first texture of type skybox, or -1."""
+    sky = np.flatnonzero(np.asarray(model.tex_type) == MGX_TEX_SKYBOX)
+    return int(sky[0]) if sky.size else -1
+
+
+class PackedRender:
+    """Holds an ``MgxRenderDesc`` (mgx_render_configure) plus the numpy arrays it points to."""
+
+    def __init__(self, model: Model):
+        A = model.arrays
+        self.arrays = {}
+        d = MgxRenderDesc()
+        d.ngeom, d.nmat, d.ntex, d.nlight = (int(model.ngeom), len(model.mat_names), len(model.tex_names),
+                                             len(model.light_names))
+        for name, kind in _RENDER_ARRAYS:
+            arr = np.ascontiguousarray(A["geom_rgba_eff" if name == "geom_rgba" else name], dtype=_NP[kind]).reshape(-1)
+            if arr.size == 0:
+                arr = np.zeros(1, dtype=_NP[kind])
+            self.arrays[name] = arr
+            setattr(d, name, arr.ctypes.data_as(_PTR[kind]))
+        d.headlight_active = int(A["headlight_active"][0])
+        d.skybox_tex = skybox_texture(model)
+        for i in range(3):
+            d.headlight_ambient[i] = float(A["headlight_ambient"][i])
+            d.headlight_diffuse[i] = float(A["headlight_diffuse"][i])
+            d.headlight_specular[i] = float(A["headlight_specular"][i])
+        self.desc = d
+
+
 class PackedModel:
     """Holds an ``MgxModelDesc`` plus the contiguous numpy arrays it points to."""
 

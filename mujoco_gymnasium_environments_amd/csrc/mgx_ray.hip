@@ -21,69 +21,18 @@
 
 using namespace mgx;
 
-#define MGX_RAY_TILE 256
-#define MGX_RAY_LDS_LIMIT (64 * 1024)
-
 namespace {
 
 // ------------------------------------------------------------------------- scene
-// reals of LDS the scene kernel binds (the arrays kinematics touches; geom poses go to the scene)
-__host__ __device__ inline int scene_lds_reals(int nq, int nbody, int njnt) { return nq + 28 * nbody + 6 * njnt; }
-
 template <typename T>
 __global__ void __launch_bounds__(64) k_ray_scene(DevModel<T> m, RayCams<T> rc, const T* gqpos, T* scene,
                                                   const uint8_t* mask) {
   const int env = blockIdx.x;
   if (mask && !mask[env]) return;
   extern __shared__ __align__(16) char smem[];
-  T* R = reinterpret_cast<T*>(smem);
-  const int nb = m.nbody, nj = m.njnt, ng = m.ngeom, l = lane_id();
-  T* sc = scene + (size_t)env * ray_scene_reals(ng, rc.ncam);
   Env<T> e;  // slim binding: only what kinematics() and geom_poses() read or write
-  int o = 0;
-  e.qpos = R + o; o += m.nq;
-  e.xpos = R + o; o += 3 * nb;
-  e.xquat = R + o; o += 4 * nb;
-  e.xmat = R + o; o += 9 * nb;
-  e.xipos = R + o; o += 3 * nb;
-  e.ximat = R + o; o += 9 * nb;
-  e.xaxis = R + o; o += 3 * nj;
-  e.xanchor = R + o;
-  e.geom_xpos = sc;
-  e.geom_xmat = sc + 3 * ng;
-  for (int k = l; k < m.nq; k += 64) e.qpos[k] = gqpos[(size_t)env * m.nq + k];
-  wsync();
-  kinematics(m, e);  // m.L.late_geom == 0 (set by the launcher): geom poses included
-  for (int c = l; c < rc.ncam; c += 64) {
-    const int b = rc.bodyid[c], mode = rc.mode[c];
-    T* out = sc + ray_scene_cam(ng, c);
-    if (mode == MGX_CAM_FIXED) {
-      T p[3], q[4];
-      mulmatvec3(p, e.xmat + 9 * b, rc.pos + 3 * c);
-      for (int k = 0; k < 3; k++) out[k] = p[k] + e.xpos[3 * b + k];
-      mulquat(q, e.xquat + 4 * b, rc.quat + 4 * c);
-      quat2mat(out + 3, q);
-    } else {
-      T base[3] = {e.xpos[3 * b], e.xpos[3 * b + 1], e.xpos[3 * b + 2]};
-      const T* off = rc.pos0 + 3 * c;
-      if (mode == MGX_CAM_TRACKCOM) {
-        // mj_comPos for this one body: the mass-weighted xipos over its DFS-contiguous subtree
-        T s0 = 0, s1 = 0, s2 = 0, ms = 0;
-        const int end = m.body_subtree_end[b];
-        for (int i = b; i < end; i++) {
-          T mi = m.body_mass[i];
-          s0 += e.xipos[3 * i] * mi; s1 += e.xipos[3 * i + 1] * mi; s2 += e.xipos[3 * i + 2] * mi;
-          ms += mi;
-        }
-        if (ms < minval<T>()) { s0 = e.xipos[3 * b]; s1 = e.xipos[3 * b + 1]; s2 = e.xipos[3 * b + 2]; }
-        else { T inv = (T)1 / ms; s0 *= inv; s1 *= inv; s2 *= inv; }
-        base[0] = s0; base[1] = s1; base[2] = s2;
-        off = rc.poscom0 + 3 * c;
-      }
-      for (int k = 0; k < 3; k++) out[k] = base[k] + off[k];
-      for (int k = 0; k < 9; k++) out[3 + k] = rc.mat0[9 * c + k];
-    }
-  }
+  ray_scene_env(m, rc, gqpos + (size_t)env * m.nq, scene + (size_t)env * ray_scene_reals(m.ngeom, rc.ncam),
+                reinterpret_cast<T*>(smem), e);
 }
 
 // ------------------------------------------------------------------------- rays
@@ -110,12 +59,7 @@ struct RayCamera {
   float* depth;                // [N][H][W], +inf for a miss (nullable)
   int* seg;                    // [N][H][W] (nullable)
   __device__ __forceinline__ void make(const T* sc, size_t, int ray, T* p, T* v) const {
-    const T* cp = sc + cam_off;
-    const int r = ray / width, c = ray - r * width;
-    const T vc[3] = {((T)2 * ((T)c + (T)0.5) / (T)width - (T)1) * t * (T)width / (T)height,
-                     ((T)1 - (T)2 * ((T)r + (T)0.5) / (T)height) * t, (T)-1};
-    for (int k = 0; k < 3; k++) p[k] = cp[k];
-    mulmatvec3(v, cp + 3, vc);
+    ray_camera_pixel(sc + cam_off, height, width, t, ray, p, v);
   }
   __device__ __forceinline__ void store(size_t at, T x, int id) const {
     if (depth) depth[at] = id < 0 ? __builtin_huge_valf() : (float)x;
@@ -136,21 +80,8 @@ __global__ void __launch_bounds__(MGX_RAY_TILE) k_ray(int ngeom, const int* geom
   int* typ = reinterpret_cast<int*>(rec + MGX_RAY_REC * ngeom);
   const T* sc = scene + (size_t)env * scene_reals;
   const int tid = threadIdx.x;
-  // stage: coalesced reads of the scene's positions and matrices and of the size table
-  for (int k = tid; k < 3 * ngeom; k += MGX_RAY_TILE) {
-    const int g = k / 3, j = k - 3 * g;
-    rec[MGX_RAY_REC * g + j] = sc[k];
-    rec[MGX_RAY_REC * g + 12 + j] = geom_size[k];
-  }
-  for (int k = tid; k < 9 * ngeom; k += MGX_RAY_TILE) {
-    const int g = k / 9, j = k - 9 * g;
-    rec[MGX_RAY_REC * g + 3 + j] = sc[3 * ngeom + k];
-  }
-  for (int g = tid; g < ngeom; g += MGX_RAY_TILE) {
-    rec[MGX_RAY_REC * g + 15] = geom_rbound[g];
-    const bool on = enable0[g] && (!enable1 || enable1[g]) && geom_bodyid[g] != bodyexclude;
-    typ[g] = on ? geom_type[g] : -1;
-  }
+  ray_stage_geoms(rec, typ, ngeom, geom_type, geom_bodyid, geom_size, geom_rbound, enable0, enable1, bodyexclude, sc,
+                  tid);
   __syncthreads();
   const int ray = blockIdx.y * MGX_RAY_TILE + tid;
   if (ray >= n_ray) return;  // tail tile (no barrier follows)
@@ -164,6 +95,9 @@ __global__ void __launch_bounds__(MGX_RAY_TILE) k_ray(int ngeom, const int* geom
 
 int ray_lds_bytes(int ngeom, int rb) { return MGX_RAY_REC * ngeom * rb + 4 * ngeom; }
 
+}  // namespace
+
+namespace mgx {
 int ray_ready(const mgx_model* m) {
   if (!m) return host_fail(MGX_E_ARG, "null model");
   if (!m->ray) return host_fail(MGX_E_ARG, "mgx_ray_configure has not been called for this model");
@@ -171,6 +105,9 @@ int ray_ready(const mgx_model* m) {
     return host_fail(MGX_E_UNSUPPORTED, "ray casting supports plane, sphere, capsule, cylinder and box geoms only");
   return MGX_OK;
 }
+}  // namespace mgx
+
+namespace {
 
 template <typename T, typename Gen>
 int launch_rays(const mgx_model* m, const DevModel<T>& M, const void* scene, const Gen& gen, int n_ray,
@@ -213,6 +150,7 @@ void upload_cams(std::vector<char>& host, const mgx_ray_desc* d, RayCams<T>& rc,
 namespace mgx {
 void ray_release(mgx_model* m) {
   if (!m || !m->ray) return;
+  render_release(m->ray);
   if (m->ray->dbuf) (void)hipFree(m->ray->dbuf);
   delete m->ray;
   m->ray = nullptr;

@@ -192,8 +192,9 @@ class RoboticArmAssemblyEnv(TaskEnv):
     metadata = {'render_modes': ['human', 'rgb_array'], 'render_fps': 50}
 
     def __init__(self, render_mode: Optional[str] = None, config: Optional[Dict] = None, device: str = "cuda:0",
-                 precision: str = "f64"):
+                 precision: str = "f64", render_camera=None, render_size=(480, 640)):
         super().__init__()
+        self._render_setup(render_camera, render_size)
         self.render_mode = render_mode
         self.config = config or {}
         self.max_episode_steps = MAX_EPISODE_STEPS
@@ -258,6 +259,8 @@ class RoboticArmAssemblyEnv(TaskEnv):
                 'success': all(prog.values())}
 
     def render(self):
+        if self._render_camera is not None:
+            return super().render()
         if self.render_mode == "rgb_array":
             return np.zeros((480, 640, 3), dtype=np.uint8)  # :494-497
         return None

@@ -20,6 +20,7 @@ from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..dynamics import DynamicsForwarding
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
+from ..render import RenderForwarding, env_frame
 from ..rollouts import RolloutForwarding
 from ..seeding import np_random
 from ..sensors import SensorForwarding
@@ -37,7 +38,7 @@ def device_actions(actions: torch.Tensor, device: torch.device) -> torch.Tensor:
     return actions
 
 
-class TaskVectorEnv(RayForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
+class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
     """``num_envs`` envs of one task stepping in lockstep on one GPU, one fused launch (or one
     staged pipeline) per env step, with same-step autoreset."""
 
@@ -169,8 +170,21 @@ class TaskEnv(EnvBase):
         torch.cuda.synchronize(v.device)
         return obs[0].cpu().numpy().copy(), float(rew[0]), bool(term[0]), bool(trunc[0])
 
+    _render_camera = None
+    _render_size = (480, 640)
+
+    def _render_setup(self, render_camera, render_size) -> None:
+        """The opt-in keywords ``render_camera`` (a camera name or index of the model; None: render()
+        stays what the reference's is on a headless node) and ``render_size`` (H, W)."""
+        self._render_camera = render_camera
+        self._render_size = (int(render_size[0]), int(render_size[1]))
+
     def render(self):
-        return None  # no viewer on a headless GPU node (the references only sync theirs)
+        if self._render_camera is None:
+            return None  # no viewer on a headless GPU node (the references only sync theirs)
+        if self.render_mode not in self.metadata['render_modes']:
+            return None
+        return env_frame(self._vec, self.render_mode, self._render_camera, self._render_size)
 
     def close(self):
         self.viewer = None

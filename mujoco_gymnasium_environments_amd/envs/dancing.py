@@ -162,8 +162,10 @@ class HumanoidDancingEnv(TaskEnv):
 
     metadata = {'render_modes': ['human', 'rgb_array'], 'render_fps': 60}
 
-    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64", **kwargs):
+    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64",
+                 render_camera=None, render_size=(480, 640), **kwargs):
         super().__init__()
+        self._render_setup(render_camera, render_size)
         self.render_mode = render_mode
         self.dt = DT
         self.max_episode_steps = MAX_EPISODE_STEPS

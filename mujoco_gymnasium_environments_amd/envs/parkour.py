@@ -206,8 +206,10 @@ class QuadrupedParkourEnv(TaskEnv):
 
     metadata = {'render_modes': ['human', 'rgb_array'], 'render_fps': 100}
 
-    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64", **kwargs):
+    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64",
+                 render_camera=None, render_size=(480, 640), **kwargs):
         super().__init__()
+        self._render_setup(render_camera, render_size)
         self.render_mode = render_mode
         self.dt = 0.01
         self.frame_skip = 10
@@ -259,6 +261,8 @@ class QuadrupedParkourEnv(TaskEnv):
         }
 
     def render(self):
+        if self._render_camera is not None:
+            return super().render()
         if self.render_mode == 'rgb_array':
             return np.zeros((480, 640, 3), dtype=np.uint8)  # parkour_env.py:835-837
         return None

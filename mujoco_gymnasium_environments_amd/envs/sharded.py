@@ -141,6 +141,37 @@ class StreamShardedEnv:
         return depth, (seg if segmentation else None)
 
     @property
+    def lights(self):
+        return self.shards[0].lights
+
+    def render_rgb(self, camera, height: int, width: int, dtype: torch.dtype = torch.uint8, depth: bool = False,
+                   segmentation: bool = False, bodyexclude: Optional[int] = None, groups=None, static: bool = True,
+                   mask: Optional[torch.Tensor] = None, stream=None):
+        """PhysicsBatch.render_rgb over every shard, into slices of one [N, H, W, 3] image (and depth /
+        segmentation when asked), each cached per shape and dtype; launched on the caller's stream only, as
+        render_depth."""
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        hw = (self.num_envs, int(height), int(width))
+        cache = self.__dict__.setdefault("_rgb_out", {})
+
+        def buf(what, shape, dt):  # each output is allocated on the first call that asks for it
+            if (what, shape, dt) not in cache:
+                cache[(what, shape, dt)] = torch.empty(shape, dtype=dt, device=self.device)
+            return cache[(what, shape, dt)]
+
+        rgb = buf("rgb", hw + (3,), dtype)
+        dep = buf("depth", hw, torch.float32) if depth else None
+        seg = buf("seg", hw, torch.int32) if segmentation else None
+        for (a, b), s in zip(self.bounds, self.shards):
+            s.batch.render_rgb(camera, height, width, dtype=dtype, depth=depth, segmentation=segmentation,
+                               bodyexclude=bodyexclude, groups=groups, static=static,
+                               mask=None if mask is None else mask[a:b], stream=cs,
+                               out=(rgb[a:b], dep[a:b] if depth else None, seg[a:b] if segmentation else None))
+        if not depth and not segmentation:
+            return rgb
+        return (rgb,) + ((dep,) if depth else ()) + ((seg,) if segmentation else ())
+
+    @property
     def sensors(self):
         return self.shards[0].sensors
 

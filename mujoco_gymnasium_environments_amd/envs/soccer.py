@@ -219,8 +219,10 @@ class HumanoidSoccerEnv(TaskEnv):
 
     metadata = {'render_modes': ['human', 'rgb_array', 'depth_array'], 'render_fps': 50}
 
-    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64", **kwargs):
+    def __init__(self, render_mode: Optional[str] = None, device: str = "cuda:0", precision: str = "f64",
+                 render_camera=None, render_size=(480, 640), **kwargs):
         super().__init__()
+        self._render_setup(render_camera, render_size)
         self.dt = 0.02
         self.max_episode_steps = MAX_EPISODE_STEPS
         self.render_mode = render_mode

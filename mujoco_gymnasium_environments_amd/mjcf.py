@@ -44,6 +44,9 @@ INTEGRATORS = {"euler": 0, "rk4": 1, "implicit": 2, "implicitfast": 3}
 CONES = {"pyramidal": 0, "elliptic": 1}
 CAM_FIXED, CAM_TRACK, CAM_TRACKCOM = 0, 1, 2   # mjtCamLight; include/mgx.h MGX_CAM_*
 CAM_MODES = {"fixed": 0, "track": 1, "trackcom": 2, "targetbody": 3, "targetbodycom": 4}
+# <texture>: tex_type / tex_builtin codes (mjtTexture, mjtBuiltin order)
+TEX_TYPES = {"2d": 0, "cube": 1, "skybox": 2}
+TEX_BUILTIN = {"none": 0, "gradient": 1, "checker": 2, "flat": 3}
 SITE_TYPES = ("sphere", "capsule", "ellipsoid", "cylinder", "box")   # site_type uses the geom numbering
 # <sensor> elements; a sensor's type code is its index here, the order of the library's list
 # (mgx_sensor_type_name, include/mgx.h MGX_SENS_*): the first 13 are computed on the device
@@ -212,6 +215,9 @@ class Model:
     site_names: List[str] = field(default_factory=list)
     cam_names: List[str] = field(default_factory=list)
     sensor_names: List[str] = field(default_factory=list)
+    light_names: List[str] = field(default_factory=list)
+    tex_names: List[str] = field(default_factory=list)
+    mat_names: List[str] = field(default_factory=list)
     nsensordata: int = 0
     geom_material: List[str] = field(default_factory=list)   # material name per geom ("" = none)
     arrays: Dict[str, np.ndarray] = field(default_factory=dict)
@@ -364,6 +370,7 @@ class _Compiler:
         geoms: List[dict] = []
         sites: List[dict] = []
         cams: List[dict] = []
+        lights: List[dict] = []
 
         def walk(elem: ET.Element, parent: int, cls: str):
             bid = len(bodies)
@@ -433,7 +440,7 @@ class _Compiler:
                              mass=float(ga["mass"]) if "mass" in ga else None,
                              group=int(ga.get("group", 0)),
                              rgba=_floats(ga.get("rgba"), 4, [0.5, 0.5, 0.5, 1.0]),
-                             material=ga.get("material", ""))
+                             own_rgba="rgba" in ga, material=ga.get("material", ""))
                     fr = _floats(ga.get("friction"), None, [1, 0.005, 0.0001])
                     if fr.size < 3:   # partial friction spec keeps the remaining defaults
                         fr = np.concatenate([fr, np.array([1, 0.005, 0.0001])[fr.size:]])
@@ -458,6 +465,8 @@ class _Compiler:
                     cams.append(dict(name=ca.get("name", ""), body=bid, mode=CAM_MODES[mode],
                                      pos=_floats(ca.get("pos"), 3, [0, 0, 0]), quat=self._orient(ca),
                                      fovy=float(ca.get("fovy", 45.0))))
+                elif ch.tag == "light":
+                    lights.append(self._light(self._attrs(ch, childcls, "light"), bid))
                 elif ch.tag == "inertial":
                     ia = dict(ch.attrib)
                     inr = dict(pos=_floats(ia.get("pos"), 3, [0, 0, 0]), quat=self._orient(ia),
@@ -774,9 +783,111 @@ class _Compiler:
         m.site_names = [s["name"] for s in sites]
         m.cam_names = [c["name"] for c in cams]
         m.geom_material = [g["material"] for g in geoms]
+        self._appearance(m, geoms, lights)
         self._sensors(m)
         _set_const(m)
         return m
+
+    @staticmethod
+    def _bool(a: Dict[str, str], key: str, default: bool) -> bool:
+        return a[key] == "true" if key in a else default
+
+    def _light(self, a: Dict[str, str], bid: int) -> dict:
+        """One <light> (body frame; MuJoCo's defaults). ``directional`` is the older spelling of
+        ``type="directional"``; cutoff is in degrees whatever the compiler's angle unit."""
+        mode = a.get("mode", "fixed")
+        if mode not in CAM_MODES:
+            raise ValueError(f"light {a.get('name', '')!r}: unknown mode {mode!r}")
+        d = _floats(a.get("dir"), 3, [0, 0, -1])
+        n = np.linalg.norm(d)
+        return dict(name=a.get("name", ""), body=bid, mode=CAM_MODES[mode],
+                    pos=_floats(a.get("pos"), 3, [0, 0, 0]), dir=d / n if n > MINVAL else np.array([0, 0, -1.0]),
+                    directional=self._bool(a, "directional", a.get("type", "spot") == "directional"),
+                    castshadow=self._bool(a, "castshadow", True), active=self._bool(a, "active", True),
+                    ambient=_floats(a.get("ambient"), 3, [0, 0, 0]), diffuse=_floats(a.get("diffuse"), 3, [0.7] * 3),
+                    specular=_floats(a.get("specular"), 3, [0.3] * 3),
+                    attenuation=_floats(a.get("attenuation"), 3, [1, 0, 0]),
+                    cutoff=float(a.get("cutoff", 45.0)), exponent=float(a.get("exponent", 10.0)))
+
+    def _appearance(self, m: Model, geoms: List[dict], lights: List[dict]) -> None:
+        """What the model says about how it looks (the render_rgb tables): lights,
+        the headlight, builtin textures, materials, and per geom the material id and the effective
+        colour — the geom's own rgba where the attribute is present (directly or through a default
+        class), else its material's rgba, else 0.5 0.5 0.5 1. ``geom_rgba`` is not touched. ``mark``
+        / ``random`` of a texture and ``reflectance`` / ``metallic`` / ``roughness`` of a material
+        are read and ignored."""
+        A = m.arrays
+        nl = len(lights)
+
+        def col(key, width, dtype=np.float64):
+            return np.array([l[key] for l in lights], dtype).reshape(nl, width) if width > 1 else \
+                np.array([l[key] for l in lights], dtype)
+
+        m.light_names = [l["name"] for l in lights]
+        A.update(dict(
+            light_bodyid=col("body", 1, np.int32), light_mode=col("mode", 1, np.int32),
+            light_pos=col("pos", 3), light_dir=col("dir", 3),
+            light_directional=col("directional", 1, np.int32), light_castshadow=col("castshadow", 1, np.int32),
+            light_active=col("active", 1, np.int32), light_ambient=col("ambient", 3), light_diffuse=col("diffuse", 3),
+            light_specular=col("specular", 3), light_attenuation=col("attenuation", 3),
+            light_cutoff=col("cutoff", 1), light_exponent=col("exponent", 1)))
+        vis = self.root.find("visual")
+        hl = vis.find("headlight") if vis is not None else None
+        ha = dict(hl.attrib) if hl is not None else {}
+        A["headlight_ambient"] = _floats(ha.get("ambient"), 3, [0.1] * 3)
+        A["headlight_diffuse"] = _floats(ha.get("diffuse"), 3, [0.4] * 3)
+        A["headlight_specular"] = _floats(ha.get("specular"), 3, [0.5] * 3)
+        A["headlight_active"] = np.array([int(ha.get("active", 1))], np.int32)
+        texs, mats = [], []
+        for asset in self.root.findall("asset"):
+            for el in asset:
+                if el.tag == "texture":
+                    a = self._attrs(el, "main", "texture")
+                    ttype, builtin = a.get("type", "cube"), a.get("builtin", "none")
+                    if ttype not in TEX_TYPES or builtin not in TEX_BUILTIN:
+                        raise ValueError(f"texture {a.get('name', '')!r}: unknown type or builtin")
+                    texs.append(dict(name=a.get("name", ""), type=TEX_TYPES[ttype], builtin=TEX_BUILTIN[builtin],
+                                     rgb1=_floats(a.get("rgb1"), 3, [0.8] * 3), rgb2=_floats(a.get("rgb2"), 3, [0.5] * 3),
+                                     file=int("file" in a)))
+        m.tex_names = [t["name"] for t in texs]
+        for asset in self.root.findall("asset"):
+            for el in asset:
+                if el.tag == "material":
+                    a = self._attrs(el, "main", "material")
+                    tex = a.get("texture", "")
+                    if tex and tex not in m.tex_names:
+                        raise ValueError(f"material {a.get('name', '')!r}: unknown texture {tex!r}")
+                    mats.append(dict(name=a.get("name", ""), rgba=_floats(a.get("rgba"), 4, [1, 1, 1, 1]),
+                                     emission=float(a.get("emission", 0)), specular=float(a.get("specular", 0.5)),
+                                     shininess=float(a.get("shininess", 0.5)),
+                                     texid=m.tex_names.index(tex) if tex else -1,
+                                     texrepeat=_floats(a.get("texrepeat"), 2, [1, 1]),
+                                     texuniform=int(a.get("texuniform", "false") == "true")))
+        m.mat_names = [t["name"] for t in mats]
+        nt, nm, ng = len(texs), len(mats), len(geoms)
+        A.update(dict(
+            tex_type=np.array([t["type"] for t in texs], np.int32),
+            tex_builtin=np.array([t["builtin"] for t in texs], np.int32),
+            tex_rgb1=np.array([t["rgb1"] for t in texs], np.float64).reshape(nt, 3),
+            tex_rgb2=np.array([t["rgb2"] for t in texs], np.float64).reshape(nt, 3),
+            tex_file=np.array([t["file"] for t in texs], np.int32),
+            mat_rgba=np.array([t["rgba"] for t in mats], np.float64).reshape(nm, 4),
+            mat_emission=np.array([t["emission"] for t in mats], np.float64),
+            mat_specular=np.array([t["specular"] for t in mats], np.float64),
+            mat_shininess=np.array([t["shininess"] for t in mats], np.float64),
+            mat_texid=np.array([t["texid"] for t in mats], np.int32),
+            mat_texrepeat=np.array([t["texrepeat"] for t in mats], np.float64).reshape(nm, 2),
+            mat_texuniform=np.array([t["texuniform"] for t in mats], np.int32)))
+        matid = np.full(ng, -1, np.int32)
+        eff = np.tile(np.array([0.5, 0.5, 0.5, 1.0]), (ng, 1))
+        for i, g in enumerate(geoms):
+            if g["material"] and g["material"] in m.mat_names:   # a name no <material> defines stays only a name
+                matid[i] = m.mat_names.index(g["material"])
+            if g["own_rgba"]:
+                eff[i] = g["rgba"]
+            elif matid[i] >= 0:
+                eff[i] = mats[matid[i]]["rgba"]
+        A["geom_matid"], A["geom_rgba_eff"] = matid, eff
 
     def _sensors(self, m: Model) -> None:
         """<sensor> in document order into the sensor_* tables (mjModel's names). Every element

@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
            "mgx_dancing.hip",
            "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip", "mgx_dyn.hip", "mgx_fd.hip",
-           "mgx_rollout.hip"]
+           "mgx_rollout.hip", "mgx_render.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
@@ -29,7 +29,8 @@ HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mg
            "mgx_ray.h", "mgx_task_host.h"]
 # task headers included by one translation unit only (so editing one rebuilds one object)
 TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_sensor.h"], "mgx_dyn.hip": ["mgx_dyn.h"],
-              "mgx_fd.hip": ["mgx_fd.h"], "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h"]}
+              "mgx_fd.hip": ["mgx_fd.h"], "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h"],
+              "mgx_render.hip": ["mgx_render.h"]}
 
 MGX_OK = 0
 MGX_F32 = 0
@@ -179,6 +180,11 @@ _SIGS = {
     "mgx_ray_scene": ([_VP, C.POINTER(cabi.MgxState), _VP, C.c_uint64, C.c_int, _VP, _VP], C.c_int),
     "mgx_ray_cast": ([_VP, _VP, _VP, _VP, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
     "mgx_ray_camera": ([_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, _VP, _VP], C.c_int),
+    "mgx_render_configure": ([_VP, C.POINTER(cabi.MgxRenderDesc)], C.c_int),
+    "mgx_render_scene_bytes": ([_VP, C.c_int], C.c_int64),
+    "mgx_render_scene": ([_VP, C.POINTER(cabi.MgxState), _VP, C.c_uint64, C.c_int, _VP, _VP], C.c_int),
+    "mgx_render_camera": ([_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, _VP, _VP],
+                          C.c_int),
     "mgx_sensor_type_name": ([C.c_int], C.c_char_p),
     "mgx_sensor_configure": ([_VP, C.POINTER(cabi.MgxSensorDesc)], C.c_int),
     "mgx_forward": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxForwardOut), C.c_int, _VP, _VP], C.c_int),

@@ -871,6 +871,75 @@ typedef struct mgx_dyn_io {
 int mgx_dynamics(const mgx_model *m, const mgx_state *state, const mgx_dyn_io *io, int n_env,
                  const uint8_t *env_mask, void *stream);
 
+/* ---- inverse kinematics (damped least squares) ------------------------------------------------ */
+/* One inverse-kinematics problem per env: the qpos that puts n_point target frames at given world
+ * poses. The targets are the points of mgx_jac: the same device tables body, kind and pos
+ * [n_point][3], shared by all envs, under the same contract (a point that breaks it contributes
+ * zeros), 1 <= n_point <= MGX_IK_MAX_POINT. quat [n_point][4] is an optional orientation offset in
+ * the body frame (NULL: identity): the target frame's orientation is xquat[body] o quat[p], so a
+ * site's or geom's own orientation is honoured.
+ * The algorithm, in the model's real type T; every sum runs in a fixed order, so results are
+ * bit-reproducible and independent of n_env:
+ *   1. q <- qpos_init (NULL: the env's current qpos). With MGX_IK_CLAMP_LIMITS every limited hinge
+ *      or slide coordinate whose dof is not masked is clamped to jnt_range.
+ *   2. for it = 0, 1, ...:
+ *      kinematics and centres of mass at q; the world point x_p of every target as mgx_jac has it;
+ *      e: the rows pos_weight_p (target_pos_p - x_p) and, where rot_weight_p > 0,
+ *         rot_weight_p rotvec(target_quat_p o conj(xquat[b_p] o quat_p)), rotvec the world-frame
+ *         rotation vector under mgx_transition_fd's convention (angle 2 atan2(|v|, w) wrapped to
+ *         (-pi, pi], 0 for a zero vector); target_quat is normalised first (a zero one is identity).
+ *         Points in order, a point's position rows before its orientation rows; a zero weight
+ *         removes its three rows, so the row count m <= 48 is the same for every env;
+ *      r = |e|_2. Stop, in this order: r not finite: status 2; r <= tol: status 0;
+ *         it == max_iter: status 1;
+ *      J: the rows pos_weight_p jacp_p and rot_weight_p jacr_p of mgx_jac, the columns of masked
+ *         dofs set to 0; A = J J' + damping^2 I (m x m), each element a dot product in dof order;
+ *      Cholesky A = L L'; a pivot that is not positive or not finite stops with status 2;
+ *      y = A^-1 e; delta = J' y, summed in row order;
+ *      s = max_d |delta_d|; if s > max_step, delta <- delta (max_step / s);
+ *      q <- mj_integratePos(q, delta, 1); the clamp of step 1 again.
+ *   3. Outputs: the last q, the last r, iters = the updates applied, status.
+ * A hinge, slide or free-translation coordinate of a masked dof, and the quaternion of a free or
+ * ball joint whose rotational dofs are all masked, keep the bits of the start.
+ * As above: nothing in mgx_state is written; rows of envs that env_mask deselects are left
+ * untouched and every byte of a selected env's non-NULL outputs is written; the call is
+ * asynchronous on the stream and neither allocates nor synchronises. Every loop is bounded by
+ * max_iter, m, nv and nbody: non-finite input ends in status 2.
+ * Not provided: posture or null-space objectives, collision avoidance, per-env weights, velocity
+ * IK, and a line search (the step is bounded by max_step only). */
+#define MGX_IK_MAX_POINT 8
+#define MGX_IK_CLAMP_LIMITS 1
+
+#define MGX_IK_CONVERGED 0  /* status: r <= tol */
+#define MGX_IK_MAX_ITER 1   /* max_iter updates applied, r > tol */
+#define MGX_IK_FAILED 2     /* non-finite residual, or a Cholesky pivot that is not positive and finite */
+
+typedef struct mgx_ik_io {
+  double pos_weight[MGX_IK_MAX_POINT];  /* >= 0 per point; 0 removes the point's position rows */
+  double rot_weight[MGX_IK_MAX_POINT];  /* >= 0 per point; 0 removes its orientation rows */
+  double damping;                /* lambda > 0 */
+  double max_step;               /* > 0: the largest |delta_d| of one update */
+  double tol;                    /* >= 0 */
+  int32_t max_iter, flags;       /* >= 0; MGX_IK_* bits */
+  const void *target_pos;        /* in  [N][n_point][3] */
+  const void *target_quat;       /* in  [N][n_point][4]; required when any rot_weight > 0 */
+  const uint8_t *dof_mask;       /* in  [nv], shared by all envs; 0: the dof may not move; NULL: all may */
+  const void *qpos_init;         /* in  [N][nq]; NULL: the env's current qpos */
+  void *qpos;                    /* out [N][nq] */
+  void *residual;                /* out [N], nullable */
+  int32_t *iters;                /* out [N], nullable */
+  int32_t *status;               /* out [N], nullable */
+} mgx_ik_io;
+
+/* MGX_E_ARG for damping <= 0, max_step <= 0, tol < 0, max_iter < 0, n_point out of range, no row
+ * (every weight 0), a negative or non-finite weight, a rot_weight > 0 without target_quat, unknown
+ * flag bits, n_env < 0, or a NULL model, state, io, qpos, target_pos, body or kind. MGX_E_CAPACITY
+ * when the per-env arrays (those of mgx_jac plus J, A, the vectors and the targets) exceed 160 KiB
+ * of LDS. */
+int mgx_ik(const mgx_model *m, const mgx_state *state, int n_point, const int32_t *body, const int32_t *kind,
+           const void *pos, const void *quat, const mgx_ik_io *io, int n_env, const uint8_t *env_mask,
+           void *stream);
+
 /* ---- finite-difference transition derivatives (MuJoCo's mjd_transitionFD / mjd_stepFD [ext]) --- */
 /* The discrete-time linearisation x' ~ A dx + B du of nsub mj_steps from the current state. The
  * state tangent is x = (dq [nv], qvel [nv]) (the models have no actuator activations), so

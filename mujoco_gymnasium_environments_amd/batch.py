@@ -15,6 +15,7 @@ import torch
 from . import cabi, mjcf
 from .native import MGX_F32, MGX_F64, check, lib
 from .dynamics import DynamicsMethods
+from .ik import IkMethods
 from .rays import RayMethods
 from .render import RenderMethods
 from .sensors import SensorMethods
@@ -62,7 +63,7 @@ class NativeModel:
             self.handle = None
 
 
-class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, TransitionMethods, RolloutMethods):
+class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

@@ -305,6 +305,19 @@ class MgxDynIO(C.Structure):
                                           "qfrc_actuator", "qfrc_external", "qfrc_inverse", "energy"]]
 
 
+MGX_IK_MAX_POINT = 8  # include/mgx.h: targets of one mgx_ik problem
+MGX_IK_CLAMP_LIMITS = 1  # mgx_ik_io.flags
+MGX_IK_CONVERGED, MGX_IK_MAX_ITER, MGX_IK_FAILED = 0, 1, 2  # mgx_ik's status
+
+
+class MgxIkIO(C.Structure):
+    _fields_ = [("pos_weight", C.c_double * MGX_IK_MAX_POINT), ("rot_weight", C.c_double * MGX_IK_MAX_POINT),
+                ("damping", C.c_double), ("max_step", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32),
+                ("flags", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ["target_pos", "target_quat", "dof_mask", "qpos_init", "qpos", "residual",
+                                          "iters", "status"]]
+
+
 MGX_FD_CENTERED = 1  # include/mgx.h mgx_fd_io.flags
 
 

@@ -1191,6 +1191,8 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
   if (r2 != MGX_OK) { delete m; return r2; }
   r2 = dyn_kernels_configure(m);
   if (r2 != MGX_OK) { delete m; return r2; }
+  r2 = ik_kernels_configure(m);
+  if (r2 != MGX_OK) { delete m; return r2; }
   if (m->wide) {
     r2 = wide_kernels_configure(m);
     if (r2 != MGX_OK) { delete m; return r2; }

@@ -25,24 +25,6 @@ using namespace mgx;
 
 namespace {
 
-// the slim binding; returns the reals taken (dyn_lds_reals)
-template <typename T>
-__device__ __forceinline__ int dyn_bind(const DevModel<T>& m, Env<T>& e, T* R, bool vel) {
-  const int nb = m.nbody, nj = m.njnt, nv = m.nv;
-  int o = 0;
-  auto take = [&](int n) { T* r = R + o; o += n; return r; };
-  e.qpos = take(m.nq);
-  e.xpos = take(3 * nb); e.xquat = take(4 * nb); e.xmat = take(9 * nb); e.xipos = take(3 * nb);
-  e.ximat = take(9 * nb); e.subtree_com = take(3 * nb); e.cinert = take(10 * nb); e.crb = take(10 * nb);
-  e.xaxis = take(3 * nj); e.xanchor = take(3 * nj); e.cdof = take(6 * nv);
-  e.qLD = take(m.nM); e.qMH = take(m.nM);  // com_crb leaves qM in qLD (nothing factors it here)
-  if (vel) {
-    e.qvel = take(nv); e.ctrl = take(m.nu); e.act_force = take(m.nu); e.xfrc = take(6 * nb);
-    e.cvel = take(6 * nb); e.cfrc = take(6 * nb); e.cdof_dot = take(6 * nv);
-  }
-  return o;
-}
-
 // ------------------------------------------------------------------------- Jacobians
 template <typename T>
 __global__ void __launch_bounds__(64) k_jac(DevModel<T> m, const T* gqpos, int P, const int* body, const int* kind,
@@ -52,7 +34,7 @@ __global__ void __launch_bounds__(64) k_jac(DevModel<T> m, const T* gqpos, int P
   if (mask && !mask[env]) return;  // the rows stay untouched
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* R = reinterpret_cast<T*>(smem);
-  const int nb = m.nbody, nv = m.nv, l = lane_id();
+  const int nv = m.nv, l = lane_id();
   Env<T> e;
   T* pt = R + dyn_bind(m, e, R, false);  // [MGX_JAC_CHUNK][4]: the point, 1 / subtree mass
   for (int k = l; k < m.nq; k += 64) e.qpos[k] = gqpos[(size_t)env * m.nq + k];
@@ -64,29 +46,12 @@ __global__ void __launch_bounds__(64) k_jac(DevModel<T> m, const T* gqpos, int P
     const int p = p0 + l;
     if (p < P) {
       const int b = body[p], k = kind[p];
-      T x[3] = {0, 0, 0}, w = 0;
-      if ((unsigned)b < (unsigned)nb) {
-        T lp[3] = {0, 0, 0};
-        if (pos) {
-          const T* q = pos + ((pos_per_env ? (size_t)env * P : (size_t)0) + p) * 3;
-          lp[0] = q[0]; lp[1] = q[1]; lp[2] = q[2];
-        }
-        if (k == MGX_JAC_WORLD) {
-          x[0] = lp[0]; x[1] = lp[1]; x[2] = lp[2];
-        } else if (k == MGX_JAC_LOCAL) {
-          mulmatvec3(x, e.xmat + 9 * b, lp);
-          for (int c = 0; c < 3; c++) x[c] += e.xpos[3 * b + c];
-        } else if (k == MGX_JAC_BODYCOM) {
-          for (int c = 0; c < 3; c++) x[c] = e.xipos[3 * b + c];
-        } else if (k == MGX_JAC_SUBTREECOM) {
-          for (int c = 0; c < 3; c++) x[c] = e.subtree_com[3 * b + c];
-          T ms = 0;
-          const int end = m.body_subtree_end[b];
-          for (int i = b; i < end; i++) ms += m.body_mass[i];
-          // a massless subtree: com_crb put its com at xipos[b]; the body-com Jacobian goes with it
-          w = ms < minval<T>() ? (T)0 : (T)1 / ms;
-        }
+      T x[3], w, lp[3] = {0, 0, 0};
+      if (pos) {
+        const T* q = pos + ((pos_per_env ? (size_t)env * P : (size_t)0) + p) * 3;
+        lp[0] = q[0]; lp[1] = q[1]; lp[2] = q[2];
       }
+      jac_point(m, e, b, k, lp, x, w);
       for (int c = 0; c < 3; c++) pt[4 * l + c] = x[c];
       pt[4 * l + 3] = w;
       if (point)
@@ -96,34 +61,11 @@ __global__ void __launch_bounds__(64) k_jac(DevModel<T> m, const T* gqpos, int P
     const int np = P - p0 < MGX_JAC_CHUNK ? P - p0 : MGX_JAC_CHUNK;
     for (int i = 0; i < np; i++) {
       const int b = body[p0 + i], k = kind[p0 + i];
-      const bool ok = (unsigned)b < (unsigned)nb && (unsigned)k <= (unsigned)MGX_JAC_SUBTREECOM;
       const T px[3] = {pt[4 * i], pt[4 * i + 1], pt[4 * i + 2]}, w = pt[4 * i + 3];
       const size_t at = ((size_t)env * P + p0 + i) * 3 * nv;
       for (int d = l; d < nv; d += 64) {
-        T jp[3] = {0, 0, 0}, jr[3] = {0, 0, 0};
-        const T* cd = e.cdof + 6 * d;
-        if (ok && k == MGX_JAC_SUBTREECOM && w > 0) {
-          // mass-weighted body-com Jacobians of the DFS-contiguous subtree, in body order
-          const int end = m.body_subtree_end[b];
-          for (int j = b; j < end; j++) {
-            if (!body_has_dof(m, j, d)) continue;
-            const T* com = e.subtree_com + 3 * m.body_rootid[j];
-            const T off[3] = {e.xipos[3 * j] - com[0], e.xipos[3 * j + 1] - com[1], e.xipos[3 * j + 2] - com[2]};
-            T t[3];
-            cross3(t, cd, off);
-            const T mj = m.body_mass[j];
-            for (int c = 0; c < 3; c++) jp[c] += mj * (cd[3 + c] + t[c]);
-          }
-          for (int c = 0; c < 3; c++) jp[c] *= w;
-        } else if (ok && body_has_dof(m, b, d)) {
-          const T* com = e.subtree_com + 3 * m.body_rootid[b];
-          const T off[3] = {px[0] - com[0], px[1] - com[1], px[2] - com[2]};
-          T t[3];
-          cross3(t, cd, off);
-          for (int c = 0; c < 3; c++) jp[c] = cd[3 + c] + t[c];
-          if (k != MGX_JAC_SUBTREECOM)
-            for (int c = 0; c < 3; c++) jr[c] = cd[c];
-        }
+        T jp[3], jr[3];
+        jac_column(m, e, b, k, px, w, d, jp, jr);
         if (jacp)
           for (int c = 0; c < 3; c++) jacp[at + (size_t)c * nv + d] = jp[c];
         if (jacr)

@@ -233,6 +233,8 @@ void sensor_release(mgx_model* m);
 int forward_kernels_configure(const mgx_model* m);
 // Jacobians and dynamics (mgx_dyn.hip): the dynamic-LDS attributes of its kernels (mgx_model_create)
 int dyn_kernels_configure(const mgx_model* m);
+// inverse kinematics (mgx_ik.hip): the dynamic-LDS attribute of its kernel (mgx_model_create)
+int ik_kernels_configure(const mgx_model* m);
 }  // namespace mgx
 
 #define MGX_WIDE_MSG "nv > 64: this model runs on the wide (two dofs per lane) kernels only"

@@ -18,6 +18,7 @@ import torch
 from .. import cabi
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..dynamics import DynamicsForwarding
+from ..ik import IkForwarding
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
 from ..render import RenderForwarding, env_frame
@@ -38,7 +39,8 @@ def device_actions(actions: torch.Tensor, device: torch.device) -> torch.Tensor:
     return actions
 
 
-class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, TransitionForwarding, RolloutForwarding):
+class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, IkForwarding, TransitionForwarding,
+                    RolloutForwarding):
     """``num_envs`` envs of one task stepping in lockstep on one GPU, one fused launch (or one
     staged pipeline) per env step, with same-step autoreset."""
 

@@ -253,6 +253,27 @@ class StreamShardedEnv:
     def energy(self, mask: Optional[torch.Tensor] = None, stream=None):
         return self.dynamics(mask=mask, stream=stream, only=("energy",)).energy
 
+    def ik_targets(self, points, **kw):
+        """PhysicsBatch.ik_targets (one targets object serves every shard, as jac_points)."""
+        return self.shards[0].batch.ik_targets(points, **kw)
+
+    def solve_ik(self, targets, target_pos: torch.Tensor, target_quat: Optional[torch.Tensor] = None,
+                 qpos_init: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, stream=None, **kw):
+        """PhysicsBatch.solve_ik over every shard: each shard's rows go into slices of one IkResult,
+        allocated once per targets object; launched on the caller's stream."""
+        from ..ik import IkResult
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        cache = self.__dict__.setdefault("_ik_out", {})
+        if id(targets) not in cache:
+            b0 = self.shards[0].batch
+            cache[id(targets)] = (targets, IkResult(self.num_envs, int(self.model.nq), b0.dtype, self.device))
+        full = cache[id(targets)][1]  # the entry keeps the targets alive, and so the key's id
+        cut = lambda x, a, b: None if x is None else x[a:b]  # noqa: E731
+        for (a, b), s in zip(self.bounds, self.shards):
+            s.batch.solve_ik(targets, target_pos[a:b], target_quat=cut(target_quat, a, b), qpos_init=cut(qpos_init, a, b),
+                             mask=cut(mask, a, b), stream=cs, out=full.rows(a, b), **kw)
+        return full
+
     def transition_fd(self, mask: Optional[torch.Tensor] = None, stream=None, only=None, **kw):
         """PhysicsBatch.transition_fd over every shard, into slices of one set of tensors."""
         from ..transitions import FD_OUTPUTS, TransitionResult, alloc_transition

@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
            "mgx_dancing.hip",
            "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip", "mgx_dyn.hip", "mgx_fd.hip",
-           "mgx_rollout.hip", "mgx_render.hip"]
+           "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
@@ -29,6 +29,7 @@ HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mg
            "mgx_ray.h", "mgx_task_host.h"]
 # task headers included by one translation unit only (so editing one rebuilds one object)
 TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_sensor.h"], "mgx_dyn.hip": ["mgx_dyn.h"],
+              "mgx_ik.hip": ["mgx_ik.h", "mgx_dyn.h"],
               "mgx_fd.hip": ["mgx_fd.h"], "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h"],
               "mgx_render.hip": ["mgx_render.h"]}
 
@@ -192,6 +193,8 @@ _SIGS = {
     "mgx_jac": ([_VP, C.POINTER(cabi.MgxState), C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int, _VP, _VP],
                 C.c_int),
     "mgx_dynamics": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxDynIO), C.c_int, _VP, _VP], C.c_int),
+    "mgx_ik": ([_VP, C.POINTER(cabi.MgxState), C.c_int, _VP, _VP, _VP, _VP, C.POINTER(cabi.MgxIkIO), C.c_int, _VP, _VP],
+               C.c_int),
     "mgx_transition_fd_bytes": ([_VP, C.c_int], C.c_int64),
     "mgx_transition_fd": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxFdIO), C.c_int, _VP, _VP], C.c_int),
     "mgx_rollout_bytes": ([_VP, C.c_int, C.c_int], C.c_int64),

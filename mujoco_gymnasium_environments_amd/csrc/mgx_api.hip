@@ -327,7 +327,7 @@ Layout make_layout(const mgx_model_desc* d, int real_bytes, int max_ncon, int ma
 // fp64 soccer, default capacity (64 contacts, 192 rows): 31.7 -> 19.7 KB per row-builder wave,
 // eight waves per CU instead of five (the VGPR limit of the row builder is also eight).
 Layout make_staged_layout(const mgx_model_desc* d, int real_bytes, int max_ncon, int max_nefc, int max_active,
-                          int gcon) {
+                          int gcon, int chain_rec) {
   Layout L{};
   int p = 0;
   const int al = 16 / real_bytes;
@@ -354,6 +354,10 @@ Layout make_staged_layout(const mgx_model_desc* d, int real_bytes, int max_ncon,
   // phase A
   L.xipos = R; L.cinert = L.xipos + a(3 * nb); L.crb = L.cinert + a(10 * nb);
   const int dead = L.crb + a(10 * nb);
+  // the joint pre-pass of kinematics (chain_rec bit 0) keeps 4 reals per joint over cinert / crb,
+  // which com_crb writes only after kinematics has finished; off when they do not cover it
+  L.jq = L.cinert;
+  L.chain_rec = 4 * nj <= dead - L.cinert ? chain_rec : chain_rec & ~1;
   L.xmat = dead; L.ximat = L.xmat + a(9 * nb); L.xaxis = L.ximat + a(9 * nb); L.xanchor = L.xaxis + a(3 * nj);
   const int endA1 = L.xanchor + a(3 * nj);
   L.cdof_dot = dead; L.cfrc = L.cdof_dot + a(6 * nv); L.act_force = L.cfrc + a(6 * nb);
@@ -395,6 +399,7 @@ Layout finisher_layout(const Layout& S, int real_bytes) {
   const int nvw = S.vec1 - S.vec0;
   L.vec0 = S.carry_reals; L.vec1 = L.vec0 + nvw; L.vec2 = L.vec1 + nvw; L.vec3 = L.vec2 + nvw;
   L.carry_lds = S.carry_reals;
+  L.chain_rec = 0;  // no chain walk in the finisher, and no cinert / crb for the pre-pass
   L.reals = L.vec3 + nvw;
   L.ints = S.carry_ints;
   L.bytes = L.reals * real_bytes + L.ints * 4;
@@ -466,6 +471,39 @@ int build_model(const mgx_model_desc* d, int device, mgx_model* out, DevModel<T>
   B.ints(d->body_dofnum, nb, &M.body_dofnum); B.ints(d->body_dofadr, nb, &M.body_dofadr);
   B.ints(d->body_subtree_end, nb, &M.body_subtree_end); B.ints(chain.data(), chain.size(), &M.body_chain);
   B.ints(depth.data(), nb, &M.body_depth);
+  {
+    // chain records (DevModel.kin_*, chain_dofw): what the chain walks gather per chain position
+    // and per joint, packed so that an entry's address depends on (body, position) or the joint only
+    std::vector<int> hi(4 * (size_t)nb * MGX_MAX_DEPTH, 0), dofw((size_t)nb * MGX_MAX_DEPTH, 0), ji(4 * (size_t)nj, 0);
+    std::vector<double> hr(8 * (size_t)nb * MGX_MAX_DEPTH, 0.0), jr(8 * (size_t)nj, 0.0);
+    for (int b = 0; b < nb; b++)
+      for (int c = 0; c < depth[b]; c++) {
+        const size_t e = (size_t)b * MGX_MAX_DEPTH + c;
+        const int i = chain[e], ja = d->body_jntadr[i], jn = d->body_jntnum[i];
+        hi[4 * e] = i; hi[4 * e + 1] = jn; hi[4 * e + 2] = ja;
+        hi[4 * e + 3] = jn == 1 && d->jnt_type[ja] == JFREE ? d->jnt_qposadr[ja] : -1;
+        for (int k = 0; k < 3; k++) hr[8 * e + k] = d->body_pos[3 * i + k];
+        for (int k = 0; k < 4; k++) hr[8 * e + 3 + k] = d->body_quat[4 * i + k];
+        const int da = d->body_dofadr[i], dn = d->body_dofnum[i];
+        int kind = -1;
+        for (int q = da; q < da + dn; q++) {
+          const int t = d->jnt_type[d->dof_jntid[q]];
+          const int kt = t == JFREE || t == JBALL ? t : JHINGE;
+          kind = kind < 0 || kind == kt ? kt : 4;
+        }
+        if (dn > 255 || (dn > 0 && da > 255)) return host_fail(MGX_E_CAPACITY, "body dof range beyond the chain records");
+        dofw[e] = dn > 0 ? (da | dn << 8 | (kind < 0 ? JHINGE : kind) << 16) : 0;
+      }
+    for (int j = 0; j < nj; j++) {
+      const int a = d->jnt_qposadr[j];
+      ji[4 * j] = d->jnt_type[j]; ji[4 * j + 1] = a;
+      for (int k = 0; k < 3; k++) { jr[8 * j + k] = d->jnt_axis[3 * j + k]; jr[8 * j + 3 + k] = d->jnt_pos[3 * j + k]; }
+      jr[8 * j + 6] = d->qpos0[a];
+    }
+    B.ints(hi.data(), hi.size(), &M.kin_hi); B.ints(ji.data(), ji.size(), &M.kin_ji);
+    B.ints(dofw.data(), dofw.size(), &M.chain_dofw);
+    B.reals(hr.data(), hr.size(), &M.kin_hr); B.reals(jr.data(), jr.size(), &M.kin_jr);
+  }
   B.add(d->body_dofmask, sizeof(uint32_t) * nb * d->nmaskword, (const void**)&M.body_dofmask);
   B.reals(d->body_pos, 3 * nb, &M.body_pos); B.reals(d->body_quat, 4 * nb, &M.body_quat);
   B.reals(d->body_ipos, 3 * nb, &M.body_ipos); B.reals(d->body_iquat, 4 * nb, &M.body_iquat);
@@ -821,6 +859,9 @@ mgx::Hooks mgx::read_hooks() {
   if (h.tail_factor < 0 || h.tail_factor > 2) h.tail_factor = 1;
   h.gcon = get("MGX_GCON", 1);
   h.rows_lds = get("MGX_ROWS_LDS", 0);
+  // MGX_CHAIN_RECORDS (Layout.chain_rec of the staged row builders): 1 the joint pre-pass of
+  // kinematics, 2 the packed chain records, 3 both, 0 neither (A/B and the bit-identity test)
+  h.chain_records = get("MGX_CHAIN_RECORDS", 3) & 3;
   return h;
 }
 
@@ -1169,7 +1210,7 @@ int mgx_model_create(const mgx_model_desc* d, int precision, int device, mgx_mod
     m->L = make_layout(d, rb, mono_ncon, mono_nefc, max_active, true);
   const bool any_staged = m->staged_ok || m->staged_rk_ok;
   m->Ls = make_staged_layout(d, rb, max_ncon, any_staged ? max_nefc : 4, m->staged_ok ? 128 : max_active,
-                             m->hooks.gcon);
+                             m->hooks.gcon, m->hooks.chain_records);
   m->Lf = finisher_layout(m->Ls, rb);
   {
     const int tight = m->hooks.tight_bp >= 0 ? (m->hooks.tight_bp != 0) : (d->npair > MGX_TIGHT_BROADPHASE_PAIRS);

@@ -74,6 +74,12 @@ struct Layout {
   // staged row builder: the contact points (3 reals per contact, written by collision, read by the
   // row blocks) live in the slot's pipe storage (Pipe.o_cpos, bind_carry_tail), not in LDS
   int gcon;
+  // staged row builder (MGX_CHAIN_RECORDS): bit 0 — kinematics computes each joint's local
+  // quantity once (lane = joint: hinge quaternion, normalised ball quaternion, slide displacement)
+  // into 4 reals per joint at jq, over cinert / crb, which nothing has written yet when kinematics
+  // runs; bit 1 — the chain walks read the packed records DevModel.kin_* / chain_dofw instead of
+  // chasing body_chain -> body_* -> jnt_* / dof_jntid -> jnt_type
+  int chain_rec, jq;
 };
 // Derived, not stored (the Layout / DevModel kernel-argument layout stays that of the task
 // kernels): wide Newton models (nv > 64, rows in global scratch) keep the per-row constraint data
@@ -129,6 +135,15 @@ struct DevModel {
   const int *actuator_trnid, *actuator_ctrllimited, *actuator_forcelimited;
   const T *actuator_gear, *actuator_ctrlrange, *actuator_forcerange, *actuator_gainprm, *actuator_biasprm;
   const T *qpos0, *qpos_spring;
+  // chain records (Layout.chain_rec bit 1), entries 16-byte aligned (kin_hi is one vector load, issued
+  // a chain position ahead; the reals stay pointer operands of body_pose_step's helpers). Per (body b,
+  // chain position c), at index b * MGX_MAX_DEPTH + c: kin_hi {body i, jntnum, jntadr, the free
+  // joint's qposadr when the body's only joint is free, else -1}, kin_hr {body_pos[3], body_quat[4],
+  // 0} and chain_dofw = dofadr | dofnum << 8 | kind << 16, kind the joint type every dof of the
+  // body shares for the cvel walk (JFREE, JBALL, JHINGE for hinges and slides), 4 when they differ.
+  // Per joint j: kin_ji {type, qposadr, 0, 0} and kin_jr {jnt_axis[3], jnt_pos[3], qpos0[qposadr], 0}.
+  const int *kin_hi, *kin_ji, *chain_dofw;
+  const T *kin_hr, *kin_jr;
   Layout L;
 };
 

@@ -48,6 +48,8 @@ struct Hooks {
                          // slots (1), for no slot (0), for every slot (2: test hook)
   int gcon = 1;          // MGX_GCON: the row builder's contact points in the pipe (0: in LDS)
   int rows_lds = 0;      // MGX_ROWS_LDS: pad the row builder's LDS (occupancy probe)
+  int chain_records = 3; // MGX_CHAIN_RECORDS: the staged row builders' chain walks (Layout.chain_rec): 1 the joint
+                         // pre-pass of kinematics, 2 the packed chain records, 3 both, 0 neither
 };
 Hooks read_hooks();
 struct RayState;  // ray casting tables (mgx_ray.h), owned by the model once mgx_ray_configure ran

@@ -7,6 +7,8 @@
 // chains into v_pk_fma with register-repacking moves, and the extra register traffic made the
 // prefetch ring wait on its own loads (measured: 188 -> 139 instructions per 4-row block, no
 // vmcnt(0) inside the sweep).
+// the staged row builders' chain walks (mgx_physics.h chain_rec): pre-pass and packed records compiled in
+#define MGX_CHAIN_RECORDS 1
 #include "mgx_internal.h"
 
 namespace mgx {

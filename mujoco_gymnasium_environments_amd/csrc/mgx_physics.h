@@ -25,6 +25,7 @@ struct Env {
   // 16-byte LDS read: [0] b, [1] f, [2] R (diagApprox until impedance), [3] 1/AR_rr,
   // [4] AR_rr, [5] aref (K*imp*(pos-margin) until the solver), [6] B damping, [7] pos
   T *efc, *efc_margin, *efc_blk;
+  T *jq;  // joint pre-pass (Layout.chain_rec bit 0): 4 reals per joint, live inside kinematics() only
   T *Bm;
   int Bs;
   T *rk;  // RK4: X[0] positions [nq] then the dX velocity vector [nv]
@@ -58,6 +59,7 @@ __device__ __forceinline__ void env_bind(const DevModel<T>& m, Env<T>& e, char* 
   e.geom_xmat = R + L.geom_xmat; e.act_force = R + L.act_force; e.cacc = R + L.cacc; e.rowc = R + L.rowc; e.con_dist = R + L.con_dist;
   e.con_pos = R + L.con_pos; e.con_frame = R + L.con_frame; e.con_mu = R + L.con_mu; e.efc = R + L.efc;
   e.efc_margin = R + L.efc_margin; e.efc_blk = R + L.efc_blk; e.Bs = L.Bstride;
+  e.jq = R + L.jq;
   if constexpr (EG) { e.efc = gB + gb_efc_off(L, sizeof(T)); e.efc_margin = gB + gb_efm_off(L, sizeof(T)); }
   if constexpr (GB) e.Bm = gB;
   else e.Bm = R + L.Bmat;
@@ -139,9 +141,66 @@ __device__ __forceinline__ bool any_bad(const T* x, int n) {
 }
 
 // ---------------------------------------------------------------- kinematics (mj_kinematics)
-// Lane b recomputes the chain root..b, so no level-by-level barriers are needed.
+// Layout.chain_rec as this translation unit sees it: the staged row builders' translation units
+// define MGX_CHAIN_RECORDS; everywhere else the walks below compile to the plain table walks alone
+// (the monolithic kernels' register budget has no room for a second loop body).
+__device__ __forceinline__ int chain_rec(const Layout& L) {
+#ifdef MGX_CHAIN_RECORDS
+  return L.chain_rec;
+#else
+  (void)L;
+  return 0;
+#endif
+}
+// 8 reals of a 16-byte aligned record, as 16-byte loads
+__device__ __forceinline__ void load_rec8(float* r, const float* p) {
+  const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+  r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w; r[4] = b.x; r[5] = b.y; r[6] = b.z; r[7] = b.w;
+}
+__device__ __forceinline__ void load_rec8(double* r, const double* p) {
+  const double2* q = reinterpret_cast<const double2*>(p);
+  const double2 a = q[0], b = q[1], c = q[2], d = q[3];
+  r[0] = a.x; r[1] = a.y; r[2] = b.x; r[3] = b.y; r[4] = c.x; r[5] = c.y; r[6] = d.x; r[7] = d.y;
+}
+
+// Joint pre-pass (Layout.chain_rec bit 0), lane = joint: the joint's local quantity, which depends
+// on qpos and the model only, once per joint instead of once per chain that holds the joint (soccer:
+// 35 joints, 164 joint evaluations over the chains, 13 hinges in series on the longest). e.jq[4 j]:
+// the hinge's axisangle2quat, the ball's normalised quaternion, or the slide's displacement in [0].
+// Free joints have no entry (no trigonometry in that path). REC: the joint's packed record.
 template <typename T>
-__device__ __forceinline__ void body_pose_step(const DevModel<T>& m, Env<T>& e, int i, T* pos, T* quat, T* mat, bool store_joints) {
+__device__ __forceinline__ void joint_prepass(const DevModel<T>& m, Env<T>& e, bool rec) {
+  for (int j = lane_id(); j < m.njnt; j += 64) {
+    int t, a;
+    T ax[3], q0;
+    if (rec) {
+      const int2 tj = *reinterpret_cast<const int2*>(m.kin_ji + 4 * j);
+      T r[8];
+      load_rec8(r, m.kin_jr + 8 * j);
+      t = tj.x; a = tj.y; ax[0] = r[0]; ax[1] = r[1]; ax[2] = r[2]; q0 = r[6];
+    } else {
+      t = m.jnt_type[j]; a = m.jnt_qposadr[j];
+      ax[0] = m.jnt_axis[3 * j]; ax[1] = m.jnt_axis[3 * j + 1]; ax[2] = m.jnt_axis[3 * j + 2];
+      q0 = t == JFREE ? (T)0 : m.qpos0[a];
+    }
+    T* o = e.jq + 4 * j;
+    if (t == JSLIDE) {
+      o[0] = e.qpos[a] - q0;
+    } else if (t == JHINGE || t == JBALL) {
+      T ql[4];
+      if (t == JBALL) { ql[0] = e.qpos[a]; ql[1] = e.qpos[a + 1]; ql[2] = e.qpos[a + 2]; ql[3] = e.qpos[a + 3]; normalize4(ql); }
+      else axisangle2quat(ql, ax, e.qpos[a] - q0);
+      o[0] = ql[0]; o[1] = ql[1]; o[2] = ql[2]; o[3] = ql[3];
+    }
+  }
+  wsync();
+}
+
+// Lane b recomputes the chain root..b, so no level-by-level barriers are needed.
+// pre: the hinge / ball quaternion and the slide displacement come from the joint pre-pass (e.jq).
+template <typename T>
+__device__ __forceinline__ void body_pose_step(const DevModel<T>& m, Env<T>& e, int i, T* pos, T* quat, T* mat, bool store_joints,
+                                               bool pre = false) {
   int ja = m.body_jntadr[i], jn = m.body_jntnum[i];
   if (jn == 1 && m.jnt_type[ja] == JFREE) {
     int a = m.jnt_qposadr[ja];
@@ -164,14 +223,69 @@ __device__ __forceinline__ void body_pose_step(const DevModel<T>& m, Env<T>& e, 
       for (int k = 0; k < 3; k++) xanchor[k] += np[k];
       int t = m.jnt_type[j];
       if (t == JSLIDE) {
-        T s = e.qpos[a] - m.qpos0[a];
+        T s = pre ? e.jq[4 * j] : e.qpos[a] - m.qpos0[a];
         for (int k = 0; k < 3; k++) np[k] += xaxis[k] * s;
       } else if (t == JHINGE || t == JBALL) {
         T ql[4], v[3];
-        if (t == JBALL) { ql[0] = e.qpos[a]; ql[1] = e.qpos[a + 1]; ql[2] = e.qpos[a + 2]; ql[3] = e.qpos[a + 3]; normalize4(ql); }
+        if (pre) { ql[0] = e.jq[4 * j]; ql[1] = e.jq[4 * j + 1]; ql[2] = e.jq[4 * j + 2]; ql[3] = e.jq[4 * j + 3]; }
+        else if (t == JBALL) { ql[0] = e.qpos[a]; ql[1] = e.qpos[a + 1]; ql[2] = e.qpos[a + 2]; ql[3] = e.qpos[a + 3]; normalize4(ql); }
         else axisangle2quat(ql, m.jnt_axis + 3 * j, e.qpos[a] - m.qpos0[a]);
         mulquat(nq, nq, ql);
         rotvecquat(v, m.jnt_pos + 3 * j, nq);
+        for (int k = 0; k < 3; k++) np[k] = xanchor[k] - v[k];
+      }
+      if (store_joints) for (int k = 0; k < 3; k++) { e.xaxis[3 * j + k] = xaxis[k]; e.xanchor[3 * j + k] = xanchor[k]; }
+    }
+    pos[0] = np[0]; pos[1] = np[1]; pos[2] = np[2];
+    quat[0] = nq[0]; quat[1] = nq[1]; quat[2] = nq[2]; quat[3] = nq[3];
+  }
+  normalize4(quat);
+  quat2mat(mat, quat);
+}
+
+// body_pose_step from the chain records (Layout.chain_rec bit 1): h is the position's kin_hi entry
+// (loaded a position ahead by the caller), hr its kin_hr entry; each joint is one kin_ji and one
+// kin_jr entry whose addresses come from the header alone. The body is body_pose_step's with the
+// table pointers replaced — the reals stay pointer operands of the same helpers in the same order,
+// so the compiler contracts the same products into the same sums and the results are the same bits
+// (with the reals loaded into registers ahead of use it did not: the states differed in the last
+// place).
+template <typename T>
+__device__ __forceinline__ void body_pose_step_rec(const DevModel<T>& m, Env<T>& e, const int4 h, const T* hr, T* pos, T* quat,
+                                                   T* mat, bool store_joints, bool pre) {
+  int ja = h.z, jn = h.y;
+  if (h.w >= 0) {
+    int a = h.w;
+    pos[0] = e.qpos[a]; pos[1] = e.qpos[a + 1]; pos[2] = e.qpos[a + 2];
+    quat[0] = e.qpos[a + 3]; quat[1] = e.qpos[a + 4]; quat[2] = e.qpos[a + 5]; quat[3] = e.qpos[a + 6];
+    normalize4(quat);
+    if (store_joints) {
+      for (int k = 0; k < 3; k++) { e.xanchor[3 * ja + k] = pos[k]; e.xaxis[3 * ja + k] = m.kin_jr[8 * ja + k]; }
+    }
+  } else {
+    T np[3], nq[4];
+    mulmatvec3(np, mat, hr);
+    for (int k = 0; k < 3; k++) np[k] += pos[k];
+    mulquat(nq, quat, hr + 3);
+    for (int j = ja; j < ja + jn; j++) {
+      const int2 tj = *reinterpret_cast<const int2*>(m.kin_ji + 4 * j);
+      const T* jr = m.kin_jr + 8 * j;  // jnt_axis, jnt_pos, qpos0
+      int a = tj.y;
+      T xaxis[3], xanchor[3];
+      rotvecquat(xaxis, jr, nq);
+      rotvecquat(xanchor, jr + 3, nq);
+      for (int k = 0; k < 3; k++) xanchor[k] += np[k];
+      int t = tj.x;
+      if (t == JSLIDE) {
+        T s = pre ? e.jq[4 * j] : e.qpos[a] - jr[6];
+        for (int k = 0; k < 3; k++) np[k] += xaxis[k] * s;
+      } else if (t == JHINGE || t == JBALL) {
+        T ql[4], v[3];
+        if (pre) { ql[0] = e.jq[4 * j]; ql[1] = e.jq[4 * j + 1]; ql[2] = e.jq[4 * j + 2]; ql[3] = e.jq[4 * j + 3]; }
+        else if (t == JBALL) { ql[0] = e.qpos[a]; ql[1] = e.qpos[a + 1]; ql[2] = e.qpos[a + 2]; ql[3] = e.qpos[a + 3]; normalize4(ql); }
+        else axisangle2quat(ql, jr, e.qpos[a] - jr[6]);
+        mulquat(nq, nq, ql);
+        rotvecquat(v, jr + 3, nq);
         for (int k = 0; k < 3; k++) np[k] = xanchor[k] - v[k];
       }
       if (store_joints) for (int k = 0; k < 3; k++) { e.xaxis[3 * j + k] = xaxis[k]; e.xanchor[3 * j + k] = xanchor[k]; }
@@ -189,12 +303,27 @@ __device__ __forceinline__ void geom_poses(const DevModel<T>& m, Env<T>& e);
 template <typename T>
 __device__ __forceinline__ void kinematics(const DevModel<T>& m, Env<T>& e) {
   int l = lane_id();
+  const int cr = chain_rec(m.L);
+  const bool pre = cr & 1;
+  if (pre) joint_prepass(m, e, (cr & 2) != 0);
   for (int b = l; b < m.nbody; b += 64) {
     T pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0}, mat[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     int depth = m.body_depth[b];
-    for (int c = 0; c < depth; c++) {
-      int i = m.body_chain[b * MGX_MAX_DEPTH + c];
-      body_pose_step(m, e, i, pos, quat, mat, i == b);
+    if (cr & 2) {
+      // position c + 1's integer header is in flight while position c is computed
+      const int4* hi = reinterpret_cast<const int4*>(m.kin_hi) + b * MGX_MAX_DEPTH;
+      const T* hrp = m.kin_hr + 8 * b * MGX_MAX_DEPTH;
+      int4 h = hi[0];
+      for (int c = 0; c < depth; c++) {
+        const int4 hn = hi[c + 1 < depth ? c + 1 : c];
+        body_pose_step_rec(m, e, h, hrp + 8 * c, pos, quat, mat, h.x == b, pre);
+        h = hn;
+      }
+    } else {
+      for (int c = 0; c < depth; c++) {
+        int i = m.body_chain[b * MGX_MAX_DEPTH + c];
+        body_pose_step(m, e, i, pos, quat, mat, i == b, pre);
+      }
     }
     for (int k = 0; k < 3; k++) e.xpos[3 * b + k] = pos[k];
     for (int k = 0; k < 4; k++) e.xquat[4 * b + k] = quat[k];
@@ -964,22 +1093,49 @@ __device__ __forceinline__ T dof_force(const DevModel<T>& m, const Env<T>& e, in
   return dof_force_applied(m, e, d, e.qfrc_applied);
 }
 
+// One chain position's dofs for the dof walks (cvel / cdof_dot, the RNE cacc walk, the rows' cacc
+// chain sums): body_chain -> body_dofadr / body_dofnum, or with the chain records (Layout.chain_rec
+// bit 1) one chain_dofw word per position, loaded a position ahead. kt: JFREE / JBALL / JHINGE
+// (hinges and slides) when every dof of the body has that joint kind, 4 when the walk looks it up
+// per dof (always without the records).
+struct ChainDofs {
+  int base, cur;
+  bool rec;
+  template <typename T>
+  __device__ __forceinline__ ChainDofs(const DevModel<T>& m, int b, bool rec_) : base(b * MGX_MAX_DEPTH), cur(0), rec(rec_) {
+    if (rec) cur = m.chain_dofw[base];
+  }
+  template <typename T>
+  __device__ __forceinline__ void next(const DevModel<T>& m, int c, int depth, int& bda, int& nd, int& kt) {
+    if (rec) {
+      const int w = cur;
+      if (c + 1 < depth) cur = m.chain_dofw[base + c + 1];
+      bda = w & 255; nd = (w >> 8) & 255; kt = w >> 16;
+    } else {
+      const int i = m.body_chain[base + c];
+      bda = m.body_dofadr[i]; nd = m.body_dofnum[i]; kt = 4;
+    }
+  }
+};
+
 // ---------------------------------------------------------------- velocity stage
 // comVel, actuator forces, RNE and its subtree sums (everything but the per-dof forces)
 template <typename T>
 __device__ __forceinline__ void velocity_bodies(const DevModel<T>& m, Env<T>& e) {
   int l = lane_id();
+  const bool rec = (chain_rec(m.L) & 2) != 0;
   // comVel: lane b walks its chain; cdof_dot for the body's own dofs
   for (int b = l; b < m.nbody; b += 64) {
     T cvel[6] = {0, 0, 0, 0, 0, 0};
     int depth = m.body_depth[b];
+    ChainDofs cw(m, b, rec);
     for (int c = 0; c < depth; c++) {
-      int i = m.body_chain[b * MGX_MAX_DEPTH + c];
-      int bda = m.body_dofadr[i], nd = m.body_dofnum[i];
-      bool own = i == b;
+      int bda, nd, kt;
+      cw.next(m, c, depth, bda, nd, kt);
+      bool own = c == depth - 1;
       for (int j = 0; j < nd; j++) {
         int dof = bda + j;
-        int t = m.jnt_type[m.dof_jntid[dof]];
+        int t = kt == 4 ? m.jnt_type[m.dof_jntid[dof]] : kt;
         if (t == JFREE) {
           if (own) for (int q = 0; q < 18; q++) e.cdof_dot[6 * dof + q] = 0;
           for (int q = 0; q < 3; q++)
@@ -1020,9 +1176,10 @@ __device__ __forceinline__ void velocity_bodies(const DevModel<T>& m, Env<T>& e)
     if (b == 0) { for (int k = 0; k < 6; k++) e.cfrc[k] = 0; continue; }
     T cacc[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
     int depth = m.body_depth[b];
+    ChainDofs cw(m, b, rec);
     for (int c = 0; c < depth; c++) {
-      int i = m.body_chain[b * MGX_MAX_DEPTH + c];
-      int bda = m.body_dofadr[i], nd = m.body_dofnum[i];
+      int bda, nd, kt;
+      cw.next(m, c, depth, bda, nd, kt);
       for (int j = 0; j < nd; j++)
         for (int k = 0; k < 6; k++) cacc[k] += e.cdof_dot[6 * (bda + j) + k] * e.qvel[bda + j];
     }

@@ -19,6 +19,8 @@
 // install it): one bank per env covers every autoreset. reset() and a reset whose bank is not ready
 // run k_pk_settle, the same stages in one wave, in this translation unit (one set of flags), so a
 // reset has one arithmetic whatever the bank count.
+// the staged row builders' chain walks (mgx_physics.h chain_rec): pre-pass and packed records compiled in
+#define MGX_CHAIN_RECORDS 1
 #include "mgx_internal.h"
 
 using namespace mgx;

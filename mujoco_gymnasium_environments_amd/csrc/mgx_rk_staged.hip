@@ -20,6 +20,8 @@
 // launches. reset() and a reset whose bank is not ready run k_rk_settle: the same stages, in one
 // wave, through the same device code and flags (one translation unit), so a reset has one
 // arithmetic whatever the bank count.
+// the staged row builders' chain walks (mgx_physics.h chain_rec): pre-pass and packed records compiled in
+#define MGX_CHAIN_RECORDS 1
 #include "mgx_internal.h"
 
 using namespace mgx;

@@ -527,9 +527,10 @@ __device__ __forceinline__ void stage_rows(const DevModel<T>& m, Env<T>& e, cons
       for (int b = l; b < m.nbody; b += 64) {
         T a[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         int depth = m.body_depth[b];
+        ChainDofs cw(m, b, (chain_rec(m.L) & 2) != 0);
         for (int c = 0; c < depth; c++) {
-          int i = m.body_chain[b * MGX_MAX_DEPTH + c];
-          int bda = m.body_dofadr[i], nd = m.body_dofnum[i];
+          int bda, nd, kt;
+          cw.next(m, c, depth, bda, nd, kt);
           for (int jd = bda; jd < bda + nd; jd++) {
             T xs = e.vec1[jd], xw = e.vec2[jd];
             const T* cd = e.cdof + 6 * jd;

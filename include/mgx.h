@@ -1062,6 +1062,81 @@ int64_t mgx_rollout_bytes(const mgx_model *m, int slots, int with_sensors);
 int mgx_rollout(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io, int n_env,
                 const uint8_t *env_mask, void *stream);
 
+/* ---- the state manifold, closed-loop rollouts (feedback on the device) ------------------------- */
+/* State rows are those of mgx_rollout: x = [time, qpos[nq], qvel[nv]], nstate = 1 + nq + nv, in the
+ * model's real type T, n_rows of them contiguous. The state tangent is that of mgx_transition_fd:
+ * dx = (dq [nv], dqvel [nv]), 2 nv reals per row.
+ *
+ * mgx_state_diff: dx[r] = xa[r] (-) xb[r] = (mj_differentiatePos(qpos_a from qpos_b), qvel_a - qvel_b).
+ *   dof d of a hinge or slide joint, or a free joint's translation: qpos_a[i] - qpos_b[i], one
+ *     subtraction in T, i the dof's qpos entry;
+ *   the three rotational dofs of a free joint, the three dofs of a ball joint: the rotation vector
+ *     of conj(q_b) o q_a, exactly mgx_transition_fd's row block 0: with (w, v) = conj(q_b) o q_a
+ *     (Hamilton product, neither quaternion normalised first), n = |v|, the vector is
+ *     v / n * ang, ang = 2 atan2(n, w), and ang - 2 pi when ang > pi (the wrap to (-pi, pi]);
+ *     n == 0 gives the zero vector. It is evaluated in double whatever T is and rounded to T once.
+ *     q_a == q_b and q_a == -q_b (component by component; q and -q are the same rotation, w = -1,
+ *     n = 0) give exactly the zero vector: that is decided before the product is formed;
+ *   dqvel = qvel_a - qvel_b in T. Time is ignored.
+ *   xb has xb_rows rows: n_rows, or 1, and then that row is used for every row of xa.
+ *
+ * mgx_state_integrate: out[r] = x[r] (+) dx[r].
+ *   out.qpos = mj_integratePos(x.qpos, dx[:nv], 1), as the step does it, in T: a hinge, slide or
+ *     free-translation entry is qpos[i] + dq[d]; a quaternion q with rotation vector w = dq[d .. d+3)
+ *     becomes normalize(q) o (cos(a / 2), sin(a / 2) w / a), a = |w|: (1, 0, 0, 0) when a == 0,
+ *     the axis (1, 0, 0) when a < 1e-15; normalize(q) leaves q alone when | |q| - 1 | <= 1e-15 and
+ *     gives (1, 0, 0, 0) when |q| < 1e-15. The product is not normalised again.
+ *   out.qvel = x.qvel + dx[nv:], out.time = x.time. out may be x itself.
+ * Both: MGX_E_ARG for a NULL model or pointer, n_rows < 0, xb_rows other than 1 or n_rows.
+ * n_rows == 0 launches nothing. Asynchronous on the stream, no allocation, no synchronisation, no
+ * atomics; every byte of dx / out is written. */
+int mgx_state_diff(const mgx_model *m, const void *xa, const void *xb, void *dx, int64_t n_rows,
+                   int64_t xb_rows, void *stream);
+int mgx_state_integrate(const mgx_model *m, const void *x, const void *dx, void *out, int64_t n_rows,
+                        void *stream);
+
+/* mgx_rollout_feedback is mgx_rollout with the control of recorded step t computed on the device
+ * from the virtual env's own state entering that step:
+ *   u[v][t][i] = u_nom[e][t][i] + alpha[e][k] k_ff[e][t][i] + sum_j gain[e][t][i][j] dx[j],
+ *   dx = mgx_state_diff(state of v entering recorded step t, x_nom[e][t]),   v = e K + k.
+ * For t = 0 that state is the initial state; for t > 0 it is row t - 1 of the `state` output. The
+ * sum over j is formed in T in a fixed order that depends on nothing but nv (bit-reproducible, not
+ * specified further); a NULL k_ff or gain drops its term (so with both NULL u is u_nom bit for
+ * bit, for every k: an open-loop rollout), a NULL alpha is 1. With MGX_FEEDBACK_CLAMP u[i] is
+ * clamped to actuator_ctrlrange where the actuator is ctrllimited, before it is stored and applied,
+ * so the recorded control is the applied one; without it u is passed on as computed and the clamp
+ * stays the step's job, as in mgx_rollout. The control is held for the nsub substeps of the step.
+ * Everything else is mgx_rollout's, read from the same mgx_rollout_io: the workspace and
+ * mgx_rollout_bytes, the passes over v, initial_state and initial_warmstart, the outputs state,
+ * sensordata and n_done, stop-and-pad on divergence, the mask rule, "every byte of a selected env's
+ * non-NULL outputs is written", asynchronous on the one stream without allocation, synchronisation
+ * or atomics. It issues one more launch per recorded step and pass than mgx_rollout.
+ *   ctrl_out  row t is u[v][t], the control applied at recorded step t;
+ *   warm_out  row t is the virtual env's qacc_warmstart entering recorded step t (row 0 is the
+ *             initial warm start): what a linearisation of that step has to start from.
+ * If the rollout diverges at step t (n_done = t), rows 0 .. t of ctrl_out and warm_out are as
+ * above and rows t + 1 .. T - 1 are zero: no control is computed after the diverging step. */
+#define MGX_FEEDBACK_CLAMP 1
+
+typedef struct mgx_feedback_io {
+  const void *u_nom;               /* in  [N][T][nu], required */
+  const void *x_nom;               /* in  [N][T][nstate]: row t is the nominal state ENTERING recorded step t; required with gain */
+  const void *k_ff;                /* in  [N][T][nu], nullable */
+  const void *alpha;               /* in  [N][K], nullable: 1 */
+  const void *gain;                /* in  [N][T][nu][2nv], nullable */
+  int32_t flags, pad0;             /* MGX_FEEDBACK_* bits */
+  void *ctrl_out;                  /* out [N][K][T][nu], nullable */
+  void *warm_out;                  /* out [N][K][T][nv], nullable */
+} mgx_feedback_io;
+
+/* MGX_E_ARG, before anything is launched and before the model or the state is looked at, for:
+ * a NULL io; a NULL fb or fb->u_nom; io->hold != 1; a non-NULL io->ctrl or MGX_ROLLOUT_SHARED_CTRL
+ * set (the nominal control comes from fb); gain without x_nom; unknown mgx_feedback_io.flags bits.
+ * Then every error of mgx_rollout. With no output requested (state, sensordata, n_done, ctrl_out
+ * and warm_out all NULL) the call returns MGX_OK and launches nothing. */
+int mgx_rollout_feedback(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io,
+                         const mgx_feedback_io *fb, int n_env, const uint8_t *env_mask, void *stream);
+
 /* ---- RGB camera images (ray-traced rgb_array) -------------------------------------------------- */
 /* The colour image of one of the model's cameras for every env, on the primary rays of
  * mgx_ray_camera. This is NOT MuJoCo's OpenGL image: it is the small shading model stated here

@@ -16,9 +16,11 @@ from . import cabi, mjcf
 from .native import MGX_F32, MGX_F64, check, lib
 from .dynamics import DynamicsMethods
 from .ik import IkMethods
+from .ilqr import IlqrMethods
 from .rays import RayMethods
 from .render import RenderMethods
 from .sensors import SensorMethods
+from .manifold import ManifoldMethods
 from .rollouts import RolloutMethods
 from .transitions import TransitionMethods
 
@@ -63,7 +65,8 @@ class NativeModel:
             self.handle = None
 
 
-class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods):
+class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods,
+                   ManifoldMethods, IlqrMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

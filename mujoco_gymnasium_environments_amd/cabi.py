@@ -338,6 +338,15 @@ class MgxRolloutIO(C.Structure):
                 ("workspace_bytes", C.c_uint64)]
 
 
+MGX_FEEDBACK_CLAMP = 1  # include/mgx.h mgx_feedback_io.flags
+
+
+class MgxFeedbackIO(C.Structure):
+    _fields_ = [("u_nom", C.c_void_p), ("x_nom", C.c_void_p), ("k_ff", C.c_void_p), ("alpha", C.c_void_p),
+                ("gain", C.c_void_p), ("flags", C.c_int32), ("pad0", C.c_int32), ("ctrl_out", C.c_void_p),
+                ("warm_out", C.c_void_p)]
+
+
 MGX_RENDER_MAX_LAYERS, MGX_RENDER_MAX_LIGHT = 4, 8  # include/mgx.h
 MGX_TEX_2D, MGX_TEX_CUBE, MGX_TEX_SKYBOX = 0, 1, 2  # mjcf.TEX_TYPES
 MGX_BUILTIN_NONE, MGX_BUILTIN_GRADIENT, MGX_BUILTIN_CHECKER, MGX_BUILTIN_FLAT = 0, 1, 2, 3  # mjcf.TEX_BUILTIN

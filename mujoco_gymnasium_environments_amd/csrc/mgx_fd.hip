@@ -13,6 +13,7 @@
 // No atomics anywhere: results are bit-reproducible.
 #include "mgx_internal.h"
 #include "mgx_fd.h"
+#include "mgx_manifold.h"
 
 using namespace mgx;
 
@@ -42,10 +43,9 @@ __global__ void __launch_bounds__(64) k_fd_expand(DevModel<T> m, mgx_state s, Fd
     const int col = (c - 1) % K;
     h = (c - 1) / K ? -eps : eps;
     if (col < nv) {
-      const int j = m.dof_jntid[col], t = m.jnt_type[j], a = m.jnt_qposadr[j], k = col - m.jnt_dofadr[j];
-      if (t == JFREE && k >= 3) { quat = a + 3; axis = k - 3; }
-      else if (t == JBALL) { quat = a; axis = k; }
-      else qa = a + k;
+      const TangentRow R = tangent_row(m, col);
+      if (R.quat >= 0) { quat = R.quat; axis = R.axis; }
+      else qa = R.qi;
     } else if (col < 2 * nv) {
       dv = col - nv;
     } else {
@@ -108,39 +108,11 @@ __global__ void __launch_bounds__(64) k_fd_expand(DevModel<T> m, mgx_state s, Fd
 }
 
 // ------------------------------------------------------------------ difference
-// Component `axis` of mj_differentiatePos for one quaternion: the rotation vector of conj(qb) o qa,
-// angle 2 atan2(|v|, w) wrapped to (-pi, pi]; a zero vector gives 0.
-// Evaluated in double whatever T is: conj(qb) o qa cancels to a vector of size |A| eps, and in
-// float the product's rounding (6e-8 of components near 1) would be 1e-4 of that at eps = 2^-10.
-__device__ __forceinline__ double fd_rotvec(const double* qa, const double* qb, int axis) {
-  const double cb[4] = {qb[0], -qb[1], -qb[2], -qb[3]};
-  double d[4];
-  mulquat(d, cb, qa);
-  const double n = sqrt(d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
-  if (n == 0) return 0;
-  double ang = 2.0 * atan2(n, d[0]);
-  if (ang > 3.14159265358979323846) ang -= 6.28318530717958647692;
-  const double x = axis == 0 ? d[1] : (axis == 1 ? d[2] : d[3]);
-  return x / n * ang;
-}
-
-// Row r of the state tangent: where it lives in a virtual env's arrays.
-struct FdRow {
-  int qi;          // >= 0: qpos[qi] (hinge, slide, free translation) or, with vel, qvel[qi]
-  int quat, axis;  // quat >= 0: component `axis` of the quaternion at qpos[quat .. quat + 4)
-  int vel;
-};
-
-// x'[r] of virtual env va minus that of vb, in the tangent space
+// x'[r] of virtual env va minus that of vb, in the tangent space (mgx_manifold.h: the rotation
+// vector of a quaternion row in double whatever T is)
 template <typename T>
-__device__ __forceinline__ T fd_delta(const FdBuf<T>& w, int nq, int nv, const FdRow& R, size_t va, size_t vb) {
-  if (R.vel) return w.qvel[va * nv + R.qi] - w.qvel[vb * nv + R.qi];
-  if (R.quat < 0) return w.qpos[va * nq + R.qi] - w.qpos[vb * nq + R.qi];
-  const T* a = w.qpos + va * nq + R.quat;
-  const T* b = w.qpos + vb * nq + R.quat;
-  const double qa[4] = {(double)a[0], (double)a[1], (double)a[2], (double)a[3]};
-  const double qb[4] = {(double)b[0], (double)b[1], (double)b[2], (double)b[3]};
-  return (T)fd_rotvec(qa, qb, R.axis);
+__device__ __forceinline__ T fd_delta(const FdBuf<T>& w, int nq, int nv, const TangentRow& R, size_t va, size_t vb) {
+  return tangent_delta<false>(R, w.qpos + va * nq, w.qvel + va * nv, w.qpos + vb * nq, w.qvel + vb * nv);
 }
 
 // One workgroup of 4 waves per env. The output's contiguous index is the column (a virtual env),
@@ -161,15 +133,7 @@ __global__ void __launch_bounds__(256) k_fd_diff(DevModel<T> m, FdBuf<T> w, int 
   if (w.A || w.B) {
     for (int r0 = 0; r0 < nx2; r0 += MGX_FD_TILE) {
       const int r = r0 + lane;
-      FdRow R{0, -1, 0, 0};
-      if (r < nv) {
-        const int j = m.dof_jntid[r], t = m.jnt_type[j], a = m.jnt_qposadr[j], k = r - m.jnt_dofadr[j];
-        if (t == JFREE && k >= 3) { R.quat = a + 3; R.axis = k - 3; }
-        else if (t == JBALL) { R.quat = a; R.axis = k; }
-        else R.qi = a + k;
-      } else if (r < nx2) {
-        R.vel = 1; R.qi = r - nv;
-      }
+      const TangentRow R = tangent_row(m, r);
       for (int c0 = 0; c0 < K; c0 += MGX_FD_TILE) {
         if (!w.A && c0 + MGX_FD_TILE <= nx2) continue;  // a tile of A only (uniform over the workgroup)
         if (!w.B && c0 >= nx2) continue;                // a tile of B only

@@ -52,6 +52,14 @@ struct RolloutBuf {
   int32_t* n_done;
   int nq, nv, nu, nx, nsd;  // nx = 6 nbody
   int K, T_steps, hold, nknot, shared;
+  T *ctrl_out, *warm_out;  // mgx_rollout_feedback's records [v][T][nu], [v][T][nv]; NULL in mgx_rollout
+};
+
+// The control law of mgx_rollout_feedback (mgx_feedback_io), typed; indexed by env e, rollout k, step t.
+template <typename T>
+struct FeedbackBuf {
+  const T *u_nom, *x_nom, *k_ff, *alpha, *gain;  // [e][t][nu], [e][t][nstate], [e][t][nu], [e][k], [e][t][nu][2nv]
+  int clamp;
 };
 
 }  // namespace mgx

@@ -1,5 +1,7 @@
 // mgx_rollout.hip — open-loop rollouts (MuJoCo's mujoco.rollout [ext]) and their C-ABI:
-// mgx_rollout_bytes, mgx_rollout (include/mgx.h).
+// mgx_rollout_bytes, mgx_rollout (include/mgx.h), and the closed-loop
+// mgx_rollout_feedback, which adds k_rollout_feedback before every mgx_step: the
+// step's ctrl from the virtual env's own state.
 //
 // Rollout k of env e is virtual env v = e K + k. A pass materialises a range of v in the caller's
 // workspace (the virtual-env workspace of mgx_transition_fd held for T steps instead of one) and
@@ -14,6 +16,7 @@
 //                     step's ctrl; on divergence n_done, the padding rows and the live flag.
 // No atomics anywhere: results are bit-reproducible.
 #include "mgx_internal.h"
+#include "mgx_manifold.h"
 #include "mgx_rollout.h"
 #include "mgx_sensor.h"
 
@@ -88,6 +91,11 @@ __global__ void __launch_bounds__(64) k_rollout_record(RolloutBuf<T> w, int v0, 
     }
   }
   if (diverged) {
+    // mgx_rollout_feedback: no control is computed after the diverging step, its rows are zero
+    if (w.ctrl_out)
+      for (size_t i = (size_t)(t + 1) * nu + l; i < (size_t)Tn * nu; i += 64) w.ctrl_out[(size_t)v * Tn * nu + i] = 0;
+    if (w.warm_out)
+      for (size_t i = (size_t)(t + 1) * nv + l; i < (size_t)Tn * nv; i += 64) w.warm_out[(size_t)v * Tn * nv + i] = 0;
     if (l == 0) {
       if (w.n_done) w.n_done[v] = t;
       w.live[b] = 0;
@@ -106,6 +114,51 @@ __global__ void __launch_bounds__(64) k_rollout_record(RolloutBuf<T> w, int v0, 
   }
 }
 
+// ------------------------------------------------------------------ feedback
+// Before recorded step t (mgx_rollout_feedback): the control of slot b from its own state,
+//   u_i = u_nom[e,t,i] + alpha[e,k] k_ff[e,t,i] + sum_j gain[e,t,i,j] dx_j,  dx = state (-) x_nom[e,t].
+// One workgroup of 4 waves per live virtual env. dx (2 nv reals) is formed once in LDS, lane =
+// tangent row; then wave w owns the actuators i = w, w + 4, ...: its lanes read row i of the gain
+// along j (coalesced), multiply by dx from LDS and sum over the lanes with a butterfly of
+// cross-lane moves, in an order fixed by the lane numbers: no atomics, bit-reproducible. The K
+// rollouts of an env sit in adjacent workgroups and read the same gain[e,t] block, so after the
+// first of them it comes from L2.
+template <typename T>
+__global__ void __launch_bounds__(256) k_rollout_feedback(DevModel<T> m, RolloutBuf<T> w, FeedbackBuf<T> f, int v0, int t) {
+  extern __shared__ double fb_smem[];
+  T* dxs = (T*)fb_smem;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (!__builtin_amdgcn_readfirstlane((int)w.live[b])) return;  // one byte, the same for every wave
+  const int v = v0 + b, env = v / w.K, nq = w.nq, nv = w.nv, nu = w.nu, nx2 = 2 * nv, Tn = w.T_steps;
+  const size_t et = (size_t)env * Tn + t, vt = (size_t)v * Tn + t;
+  if (f.gain) {
+    const T* xn = f.x_nom + et * ((size_t)1 + nq + nv);
+    const T* q = w.qpos + (size_t)b * nq;
+    const T* qv = w.qvel + (size_t)b * nv;
+    for (int r = tid; r < nx2; r += 256) dxs[r] = tangent_delta<true>(tangent_row(m, r), q, qv, xn + 1, xn + 1 + nq);
+  }
+  if (w.warm_out)
+    for (int i = tid; i < nv; i += 256) w.warm_out[vt * nv + i] = w.qacc[(size_t)b * nv + i];
+  __syncthreads();
+  const T al = f.alpha ? f.alpha[v] : (T)1;
+  for (int i = wave; i < nu; i += 4) {
+    T acc = 0;
+    if (f.gain) {
+      const T* g = f.gain + (et * nu + i) * nx2;
+      for (int j = lane; j < nx2; j += 64) acc += g[j] * dxs[j];
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    }
+    if (lane == 0) {
+      T u = f.u_nom[et * nu + i];
+      if (f.k_ff) u += al * f.k_ff[et * nu + i];
+      if (f.gain) u += acc;
+      if (f.clamp && m.actuator_ctrllimited[i]) u = clampv(u, m.actuator_ctrlrange[2 * i], m.actuator_ctrlrange[2 * i + 1]);
+      w.ctrl[(size_t)b * nu + i] = u;
+      if (w.ctrl_out) w.ctrl_out[vt * nu + i] = u;
+    }
+  }
+}
+
 int rollout_dims(const mgx_model* m, RolloutDims* d) {
   mgx_model_info info;
   const int rc = mgx_model_get_info(m, &info);
@@ -117,8 +170,8 @@ int rollout_dims(const mgx_model* m, RolloutDims* d) {
 }
 
 template <typename T>
-int run_rollout(const mgx_model* m, const RolloutDims& d, const mgx_state* s, const mgx_rollout_io* io, bool sensors,
-                int n_env, const uint8_t* mask, hipStream_t st) {
+int run_rollout(const mgx_model* m, const DevModel<T>& M, const RolloutDims& d, const mgx_state* s, const mgx_rollout_io* io,
+                const mgx_feedback_io* fio, bool sensors, int n_env, const uint8_t* mask, hipStream_t st) {
   const RolloutLayout o = rollout_layout(d, io->slots, sensors);
   char* ws = (char*)io->workspace;
   const int Tn = io->n_step, K = io->n_roll;
@@ -132,6 +185,13 @@ int run_rollout(const mgx_model* m, const RolloutDims& d, const mgx_state* s, co
   w.nq = d.nq; w.nv = d.nv; w.nu = d.nu; w.nx = 6 * d.nbody; w.nsd = d.nsd;
   w.K = K; w.T_steps = Tn; w.hold = io->hold; w.nknot = (Tn + io->hold - 1) / io->hold;
   w.shared = io->flags & MGX_ROLLOUT_SHARED_CTRL ? 1 : 0;
+  FeedbackBuf<T> f{};
+  if (fio) {
+    w.ctrl_out = (T*)fio->ctrl_out; w.warm_out = (T*)fio->warm_out;
+    f.u_nom = (const T*)fio->u_nom; f.x_nom = (const T*)fio->x_nom; f.k_ff = (const T*)fio->k_ff;
+    f.alpha = (const T*)fio->alpha; f.gain = (const T*)fio->gain; f.clamp = fio->flags & MGX_FEEDBACK_CLAMP ? 1 : 0;
+  }
+  const size_t fb_lds = (size_t)(2 * d.nv > 0 ? 2 * d.nv : 1) * sizeof(double);
   mgx_state vs{};
   vs.qpos = w.qpos; vs.qvel = w.qvel; vs.qacc_warmstart = w.qacc; vs.ctrl = w.ctrl; vs.qfrc_applied = w.qfrc;
   vs.xfrc_applied = w.xfrc; vs.time = w.time; vs.warning = w.warning; vs.overflow = w.overflow;
@@ -151,6 +211,11 @@ int run_rollout(const mgx_model* m, const RolloutDims& d, const mgx_state* s, co
     for (int t = 0; t < Tn; t++) {
       // the library's own step, exactly as a caller of mgx_step gets it; rollouts of deselected
       // envs hold no state, and diverged ones are done: both are masked out by the live flags
+      if (fio) {
+        // the control of this step from the state entering it; the open-loop path launches nothing here
+        hipLaunchKernelGGL(k_rollout_feedback<T>, dim3(cnt), dim3(256), fb_lds, st, M, w, f, (int)v0, t);
+        MGX_HIPCHK(hipGetLastError());
+      }
       int rc = mgx_step(m, &vs, nullptr, cnt, io->nsub, w.live, st);
       if (rc) return rc;
       if (sensors) {
@@ -180,8 +245,13 @@ int64_t mgx_rollout_bytes(const mgx_model* m, int slots, int with_sensors) {
   return (int64_t)rollout_layout(d, slots, with_sensors != 0).bytes;
 }
 
-int mgx_rollout(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, int n_env, const uint8_t* env_mask,
-                void* stream) {
+}  // extern "C"
+
+namespace {
+
+// mgx_rollout, and mgx_rollout_feedback with its checked mgx_feedback_io
+int rollout_call(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fio, int n_env,
+                 const uint8_t* env_mask, void* stream) {
   if (!m || !io || n_env < 0) return host_fail(MGX_E_ARG, "null argument or n_env < 0");
   int rc = host_check_state(s);
   if (rc) return rc;
@@ -205,10 +275,34 @@ int mgx_rollout(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io
   if (rc) return rc;
   if (!io->workspace || io->workspace_bytes < rollout_layout(d, io->slots, io->sensordata != nullptr).bytes)
     return host_fail(MGX_E_ARG, "workspace smaller than mgx_rollout_bytes");
-  if (n_env == 0 || (!io->state && !sensors && !io->n_done)) return MGX_OK;
+  const bool records = fio && (fio->ctrl_out || fio->warm_out);
+  if (n_env == 0 || (!io->state && !sensors && !io->n_done && !records)) return MGX_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32) return run_rollout<float>(m, d, s, io, sensors, n_env, env_mask, st);
-  return run_rollout<double>(m, d, s, io, sensors, n_env, env_mask, st);
+  if (m->precision == MGX_F32) return run_rollout<float>(m, m->mf, d, s, io, fio, sensors, n_env, env_mask, st);
+  return run_rollout<double>(m, m->md, d, s, io, fio, sensors, n_env, env_mask, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgx_rollout(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, int n_env, const uint8_t* env_mask,
+                void* stream) {
+  return rollout_call(m, s, io, nullptr, n_env, env_mask, stream);
+}
+
+// The checks that concern the feedback law read io and fb only and come first, so a caller's
+// mistake in them is named whatever the model and the state are.
+int mgx_rollout_feedback(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fb,
+                         int n_env, const uint8_t* env_mask, void* stream) {
+  if (!io) return host_fail(MGX_E_ARG, "null mgx_rollout_io");
+  if (!fb || !fb->u_nom) return host_fail(MGX_E_ARG, "mgx_rollout_feedback needs an mgx_feedback_io with u_nom");
+  if (io->hold != 1) return host_fail(MGX_E_ARG, "mgx_rollout_feedback: hold must be 1");
+  if (io->ctrl || (io->flags & MGX_ROLLOUT_SHARED_CTRL))
+    return host_fail(MGX_E_ARG, "mgx_rollout_feedback: io->ctrl must be NULL and MGX_ROLLOUT_SHARED_CTRL unset (the nominal control is fb->u_nom)");
+  if (fb->gain && !fb->x_nom) return host_fail(MGX_E_ARG, "mgx_feedback_io.gain needs x_nom");
+  if (fb->flags & ~MGX_FEEDBACK_CLAMP) return host_fail(MGX_E_ARG, "unknown mgx_feedback_io.flags bits");
+  return rollout_call(m, s, io, fb, n_env, env_mask, stream);
 }
 
 }  // extern "C"

@@ -19,9 +19,11 @@ from .. import cabi
 from ..batch import PhysicsBatch, _ptr, stream_handle
 from ..dynamics import DynamicsForwarding
 from ..ik import IkForwarding
+from ..ilqr import IlqrForwarding
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
 from ..render import RenderForwarding, env_frame
+from ..manifold import ManifoldForwarding
 from ..rollouts import RolloutForwarding
 from ..seeding import np_random
 from ..sensors import SensorForwarding
@@ -40,7 +42,7 @@ def device_actions(actions: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, IkForwarding, TransitionForwarding,
-                    RolloutForwarding):
+                    RolloutForwarding, ManifoldForwarding, IlqrForwarding):
     """``num_envs`` envs of one task stepping in lockstep on one GPU, one fused launch (or one
     staged pipeline) per env step, with same-step autoreset."""
 

@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
            "mgx_dancing.hip",
            "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip", "mgx_dyn.hip", "mgx_fd.hip",
-           "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip"]
+           "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip", "mgx_manifold.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
@@ -30,7 +30,8 @@ HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mg
 # task headers included by one translation unit only (so editing one rebuilds one object)
 TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_sensor.h"], "mgx_dyn.hip": ["mgx_dyn.h"],
               "mgx_ik.hip": ["mgx_ik.h", "mgx_dyn.h"],
-              "mgx_fd.hip": ["mgx_fd.h"], "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h"],
+              "mgx_fd.hip": ["mgx_fd.h", "mgx_manifold.h"],
+              "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h", "mgx_manifold.h"], "mgx_manifold.hip": ["mgx_manifold.h"],
               "mgx_render.hip": ["mgx_render.h"]}
 
 MGX_OK = 0
@@ -199,6 +200,10 @@ _SIGS = {
     "mgx_transition_fd": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxFdIO), C.c_int, _VP, _VP], C.c_int),
     "mgx_rollout_bytes": ([_VP, C.c_int, C.c_int], C.c_int64),
     "mgx_rollout": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxRolloutIO), C.c_int, _VP, _VP], C.c_int),
+    "mgx_state_diff": ([_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP], C.c_int),
+    "mgx_state_integrate": ([_VP, _VP, _VP, _VP, C.c_int64, _VP], C.c_int),
+    "mgx_rollout_feedback": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxRolloutIO),
+                              C.POINTER(cabi.MgxFeedbackIO), C.c_int, _VP, _VP], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

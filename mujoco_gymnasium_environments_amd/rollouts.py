@@ -184,6 +184,122 @@ class RolloutMethods:
         return res
 
 
+    def rollout_feedback(self, u_nom: torch.Tensor, x_nom: Optional[torch.Tensor] = None,
+                         k_ff: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
+                         gain: Optional[torch.Tensor] = None, clamp: bool = True,
+                         initial_state: Optional[torch.Tensor] = None, initial_warmstart: Optional[torch.Tensor] = None,
+                         nsub: int = 1, sensordata: bool = False, mask: Optional[torch.Tensor] = None, stream=None,
+                         slots: Optional[int] = None, only: Optional[Sequence[str]] = None,
+                         out: Optional["FeedbackRolloutResult"] = None) -> "FeedbackRolloutResult":
+        """``FeedbackRolloutResult(state, sensordata, n_done, ctrl, warmstart)``: K closed-loop
+        rollouts of T recorded steps per (masked) env. ``rollout`` with the control of every step
+        computed on the device from the rollout's own state entering that step:
+
+            u[n, k, t] = u_nom[n, t] + alpha[n, k] k_ff[n, t] + gain[n, t] @ (x[n, k, t] (-) x_nom[n, t])
+
+        ``u_nom`` [N, T, nu]; ``x_nom`` [N, T, nstate] (row t: the nominal state ENTERING step t,
+        required with ``gain``); ``k_ff`` [N, T, nu]; ``alpha`` [N, K] (default 1); ``gain``
+        [N, T, nu, 2nv]; ``(-)`` is ``state_difference``. ``clamp`` clamps u to the control range of
+        limited actuators before it is recorded and applied. K comes from ``alpha`` or
+        ``initial_state`` / ``initial_warmstart``, else 1; T from ``u_nom``. ``ctrl`` [N, K, T, nu]
+        is the control applied at step t, ``warmstart`` [N, K, T, nv] the qacc_warmstart entering
+        it; after a divergence at step n_done their later rows are zero. Everything else
+        (``initial_state``, ``nsub``, ``sensordata``, ``mask``, ``slots``, ``only``, ``out``) is
+        ``rollout``'s; nothing is written to the batch's state."""
+        n, m = self.n, self.model
+        nq, nv, nu, ns = int(m.nq), int(m.nv), int(m.nu), self.state_size
+        if u_nom.dim() != 3 or u_nom.shape[0] != n or u_nom.shape[2] != nu:
+            raise ValueError(f"u_nom must be [N, T, nu], got {tuple(u_nom.shape)}")
+        t = int(u_nom.shape[1])
+        if gain is not None and x_nom is None:
+            raise ValueError("gain needs x_nom")
+        for name, x, shape in (("x_nom", x_nom, (n, t, ns)), ("k_ff", k_ff, (n, t, nu)), ("gain", gain, (n, t, nu, 2 * nv))):
+            if x is not None and tuple(x.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)}, got {tuple(x.shape)}")
+        if alpha is not None and (alpha.dim() != 2 or alpha.shape[0] != n):
+            raise ValueError(f"alpha must be [N, K], got {tuple(alpha.shape)}")
+        k = None if alpha is None else int(alpha.shape[1])
+        for name, x in (("initial_state", initial_state), ("initial_warmstart", initial_warmstart)):
+            if x is None:
+                continue
+            if x.dim() != 3 or x.shape[0] != n or (k is not None and x.shape[1] != k):
+                raise ValueError(f"{name} must be [N, K, width] with the K of the other arguments, got {tuple(x.shape)}")
+            k = int(x.shape[1])
+        k = 1 if k is None else k
+        for name, x, width in (("u_nom", u_nom, nu), ("x_nom", x_nom, ns), ("k_ff", k_ff, nu), ("alpha", alpha, k),
+                               ("gain", gain, 2 * nv), ("initial_state", initial_state, ns),
+                               ("initial_warmstart", initial_warmstart, nv)):
+            if x is not None:
+                assert x.dtype == self.dtype and x.is_cuda and x.is_contiguous() and x.shape[-1] == width, name
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.numel() == n and mask.is_cuda and mask.is_contiguous()
+        fields = ROLLOUT_OUTPUTS + FEEDBACK_OUTPUTS
+        want = [f for f in fields if sensordata or f != "sensordata"] if only is None else list(only)
+        for f in want:
+            if f not in fields:
+                raise KeyError(f"unknown rollout output {f!r}; there are {list(fields)}")
+        sensordata = "sensordata" in want
+        nsd = int(m.nsensordata)
+        if sensordata:
+            self._sensor_ready()
+        if out is None:
+            cache = self.__dict__.setdefault("_feedback_out", {})
+            key = (k, t, sensordata)
+            if key not in cache and t >= 1:
+                cache[key] = alloc_feedback_rollout(n, k, t, ns, nsd, nv, nu, self.dtype, self.device, sensordata)
+            out = cache.get(key) or FeedbackRolloutResult()
+        slots, ws = self._rollout_workspace(slots, sensordata, max(n * k, 1))
+        io = cabi.MgxRolloutIO()
+        io.n_roll, io.n_step, io.nsub, io.hold, io.flags = k, t, int(nsub), 1, 0
+        io.slots, io.workspace, io.workspace_bytes = slots, ws.data_ptr(), ws.numel()
+        io.initial_state = None if initial_state is None else initial_state.data_ptr()
+        io.initial_warmstart = None if initial_warmstart is None else initial_warmstart.data_ptr()
+        ptr = lambda x: None if x is None else (x.data_ptr() or ws.data_ptr())  # noqa: E731  (nu = 0: no bytes)
+        fb = cabi.MgxFeedbackIO()
+        fb.u_nom, fb.x_nom, fb.k_ff, fb.alpha, fb.gain = ptr(u_nom), ptr(x_nom), ptr(k_ff), ptr(alpha), ptr(gain)
+        fb.flags = cabi.MGX_FEEDBACK_CLAMP if clamp else 0
+        res = FeedbackRolloutResult()
+        widths = {"state": (k, t, ns), "sensordata": (k, t, nsd), "n_done": (k,), "ctrl": (k, t, nu), "warmstart": (k, t, nv)}
+        native_name = {"ctrl": "ctrl_out", "warmstart": "warm_out"}
+        for f in want:
+            x = getattr(out, f)
+            if x is None:
+                continue
+            assert x.is_contiguous() and tuple(x.shape) == (n,) + widths[f], (f, tuple(x.shape))
+            assert x.dtype == (torch.int32 if f == "n_done" else self.dtype)
+            setattr(fb if f in native_name else io, native_name.get(f, f), x.data_ptr() or ws.data_ptr())
+            setattr(res, f, x)
+        check(lib().mgx_rollout_feedback(self.native.handle, C.byref(self._state), C.byref(io), C.byref(fb), n, _ptr(mask),
+                                         _stream(stream)), "mgx_rollout_feedback")
+        return res
+
+
+FEEDBACK_OUTPUTS = ("ctrl", "warmstart")
+
+
+class FeedbackRolloutResult:
+    """The fields of :class:`RolloutResult` plus ctrl [N, K, T, nu] (the control applied at recorded
+    step t) and warmstart [N, K, T, nv] (the qacc_warmstart entering it); rows after a divergence
+    (t > n_done) of these two are zero."""
+
+    __slots__ = ROLLOUT_OUTPUTS + FEEDBACK_OUTPUTS
+
+    def __init__(self, **fields):
+        for f in self.__slots__:
+            setattr(self, f, fields.get(f))
+
+    def rows(self, a: int, b: int) -> "FeedbackRolloutResult":
+        return FeedbackRolloutResult(**{f: None if getattr(self, f) is None else getattr(self, f)[a:b]
+                                        for f in self.__slots__})
+
+
+def alloc_feedback_rollout(n, k, t, nstate, nsensordata, nv, nu, dtype, device, sensordata=True) -> FeedbackRolloutResult:
+    base = alloc_rollout(n, k, t, nstate, nsensordata, dtype, device, sensordata)
+    z = lambda *shape: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+    return FeedbackRolloutResult(state=base.state, sensordata=base.sensordata, n_done=base.n_done, ctrl=z(n, k, t, nu),
+                                 warmstart=z(n, k, t, nv))
+
+
 class RolloutForwarding:
     """Mixin of the ``*VectorEnv`` classes: the batch's open-loop rollouts under the env's name.
 
@@ -207,3 +323,8 @@ class RolloutForwarding:
     def physics_rollout(self, **kw):
         """PhysicsBatch.rollout of this env's batch (raw actuator ctrl; ``nsub`` = frame skip)."""
         return self.batch.rollout(**kw)
+
+    def physics_rollout_feedback(self, u_nom, **kw):
+        """PhysicsBatch.rollout_feedback of this env's batch (closed-loop: the control of every step
+        from the rollout's own state; raw actuator ctrl; ``nsub`` = frame skip)."""
+        return self.batch.rollout_feedback(u_nom, **kw)

@@ -119,8 +119,70 @@ class TransitionMethods:
         return res
 
 
+    def transition_fd_along(self, state0: torch.Tensor, ctrl: torch.Tensor, warmstart: Optional[torch.Tensor] = None,
+                            eps: Optional[float] = None, centered: bool = False, nsub: int = 1,
+                            slots: Optional[int] = None) -> "TrajectoryTransitionResult":
+        """``transition_fd`` at the T states of a trajectory per env: ``state0`` [N, T, nstate] (the
+        state ENTERING each step, e.g. a rollout's initial state followed by its ``state[:, k, :-1]``),
+        ``ctrl`` [N, T, nu] and ``warmstart`` [N, T, nv] (a closed-loop rollout's ``warmstart``; the
+        solvers run a bounded number of iterations from it, so a linearisation of the step the
+        rollout took must start from the one it had; default: the env's own at every t). Returns A
+        [N, T, 2nv, 2nv], B [N, T, 2nv, nu], next_state [N, T, nstate] and warning int32 [N, T].
+
+        The existing mgx_transition_fd runs over the N T stacked rows, held in a second batch that
+        shares this one's compiled model, with each env's qfrc_applied and xfrc_applied repeated.
+        Nothing is written to this batch's state. Tensors are owned by the batch and overwritten by
+        the next call with the same T."""
+        from .batch import PhysicsBatch
+        n, m = self.n, self.model
+        nq, nv, nu, ns = int(m.nq), int(m.nv), int(m.nu), 1 + int(m.nq) + int(m.nv)
+        if state0.dim() != 3 or state0.shape[0] != n or state0.shape[2] != ns:
+            raise ValueError(f"state0 must be [N, T, nstate], got {tuple(state0.shape)}")
+        t = int(state0.shape[1])
+        if tuple(ctrl.shape) != (n, t, nu):
+            raise ValueError(f"ctrl must be [N, T, nu] = {[n, t, nu]}, got {tuple(ctrl.shape)}")
+        if warmstart is not None and tuple(warmstart.shape) != (n, t, nv):
+            raise ValueError(f"warmstart must be [N, T, nv] = {[n, t, nv]}, got {tuple(warmstart.shape)}")
+        cache = self.__dict__.setdefault("_fd_along", {})
+        if t not in cache:
+            cache[t] = PhysicsBatch(m, n * t, precision="f64" if self.dtype == torch.float64 else "f32",
+                                    device=str(self.device), native=self.native)
+        tb = cache[t]
+        x = state0.to(self.dtype).reshape(n * t, ns)
+        tb.time.copy_(x[:, 0])
+        tb.qpos.copy_(x[:, 1:1 + nq])
+        tb.qvel.copy_(x[:, 1 + nq:])
+        tb.ctrl[:, :nu] = ctrl.to(self.dtype).reshape(n * t, nu)
+        tb.qacc_warmstart.copy_(self.qacc_warmstart.repeat_interleave(t, dim=0) if warmstart is None
+                                else warmstart.to(self.dtype).reshape(n * t, nv))
+        tb.qfrc_applied.copy_(self.qfrc_applied.repeat_interleave(t, dim=0))
+        tb.xfrc_applied.copy_(self.xfrc_applied.repeat_interleave(t, dim=0))
+        r = tb.transition_fd(eps=eps, centered=centered, nsub=nsub, slots=slots)
+        # the step advances time by nsub timesteps, as mgx_step does it: one add in T per substep
+        time = x[:, 0].clone()
+        for _ in range(int(nsub)):
+            time += torch.tensor(float(m.timestep), dtype=self.dtype, device=self.device)
+        nxt = torch.cat([time[:, None], r.next_qpos, r.next_qvel], dim=1)
+        return TrajectoryTransitionResult(A=r.A.view(n, t, 2 * nv, 2 * nv), B=r.B.view(n, t, 2 * nv, nu),
+                                          next_state=nxt.view(n, t, ns), warning=r.warning.view(n, t))
+
+
+class TrajectoryTransitionResult:
+    """A [N, T, 2nv, 2nv], B [N, T, 2nv, nu], next_state [N, T, nstate] (the nominal state after each
+    step) and warning int32 [N, T] of ``transition_fd_along``."""
+
+    __slots__ = ("A", "B", "next_state", "warning")
+
+    def __init__(self, A, B, next_state, warning):
+        self.A, self.B, self.next_state, self.warning = A, B, next_state, warning
+
+
 class TransitionForwarding:
     """Mixin of the ``*VectorEnv`` classes: the batch's ``transition_fd`` under the env's name."""
+
+    def transition_fd_along(self, state0, ctrl, **kw):
+        """PhysicsBatch.transition_fd_along of this env's batch."""
+        return self.batch.transition_fd_along(state0, ctrl, **kw)
 
     def transition_fd(self, **kw):
         """PhysicsBatch.transition_fd of this env's batch (derivatives of its physics step; pass

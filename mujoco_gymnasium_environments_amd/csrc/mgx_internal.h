@@ -1,10 +1,13 @@
 // mgx_internal.h — host-side definitions shared by the translation units of libmgx.so
-// (mgx_api.hip: model, physics and soccer; mgx_step.hip: generic step; mgx_parkour.hip:
-// quadruped_parkour; mgx_bipedal.hip: bipedal_rescue; mgx_dancing.hip: humanoid_dancing;
-// mgx_task_host.h: the checks and the kernel dispatch the task entries share).
+// (mgx_api.hip: the model; mgx_staged_host.hip: what the staged tasks' hosts share; mgx_soccer.hip:
+// humanoid_soccer; mgx_step.hip: generic step; mgx_parkour.hip: quadruped_parkour; mgx_bipedal.hip:
+// bipedal_rescue; mgx_dancing.hip: humanoid_dancing; mgx_task_host.h: the checks and the kernel
+// dispatch the task entries share).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <mutex>
 #include <string>
 #include <type_traits>
 
@@ -123,6 +126,8 @@ int host_check_state(const mgx_state* s);
 int host_check_scratch(const mgx_model* m, const mgx_state* s);
 // dynamic-LDS attributes of the generic step kernels (mgx_step.hip)
 int step_kernels_configure(const mgx_model* m);
+// ... of the soccer kernels and, for a staged model, of the staged pipeline's (mgx_soccer.hip)
+int soccer_kernels_configure(const mgx_model* m);
 // the staged solver S2 (mgx_pgs.hip)
 template <typename T>
 void launch_pgs(const Pipe& P, int slots, int lds, hipStream_t st, int maxit, T tol, T scale, int big, const Hooks& h,
@@ -148,7 +153,7 @@ void launch_soccer_settle(const DevModel<T>& Ms, const DevModel<T>& Mf, const So
                           const uint8_t* mask, const Pipe& P, int mode, int grid, int lds, hipStream_t st, int maxit, T tol,
                           T scale);
 int staged_kernels_configure(int precision, int ls, int lf, int settle);
-// staged-step workspace layout (mgx_api.hip) and the LDS of one solver wave holding `rows` rows
+// staged-step workspace layout (mgx_staged_host.hip) and the LDS of one solver wave holding `rows` rows
 // per slot with `lps` lanes per slot and `tw` table words per block
 // split_default: the pipeline's row-split threshold in blocks when MGX_PGS_SPLIT_BLOCKS is not set
 // (Pipe.split_blocks; 0: off)
@@ -157,6 +162,8 @@ size_t make_staged_pipe(const mgx_model* m, void* ws, int n_env, int banks, Pipe
 // sqg: row scalars in the pipe, only the forces in LDS (the RK4 pipeline; soccer at full capacity)
 // twl: block-table words per block in LDS (mgx_twl: 8 for the 8-dof group layout, 4 dof-granular)
 int staged_pgs_lds_bytes(const mgx_model* m, int rows, int lps, int sqg, int twl);
+// LDS of the soccer wide launch's one-slot waves with B in LDS, 0 when B stays in global memory
+int wide_arena_bytes(const mgx_model* m);
 // LDS of a one-wave settle: the row builder's layout, then one solver wave with maxE rows per slot,
 // then the finisher's layout, in turn
 int staged_settle_lds(const mgx_model* m, const Pipe& P, int lps, int sqg, int twl);
@@ -185,6 +192,21 @@ struct SideStream {
   hipEvent_t rows, big;
 };
 SideStream* side_stream(hipStream_t st);
+// The cache behind such streams: one X (a stream and its events) per (caller stream, device), made
+// by create(X&) on first use and kept for the process; nullptr is cached when create refuses.
+template <typename X, typename Create>
+X* stream_cache(hipStream_t st, Create create) {
+  static std::mutex mu;
+  static std::map<std::pair<hipStream_t, int>, X*> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find({st, dev});
+  if (it != cache.end()) return it->second;
+  X* x = new X{};
+  if (!create(*x)) { delete x; x = nullptr; }
+  return cache[{st, dev}] = x;
+}
 // What a staged task's workspace entries differ in: its name in the messages, the model check and
 // its refusal (init_checks: mgx_<task>_workspace_init makes that check too), its make_staged_pipe
 // parameters and its checkAcc template kernels, indexed by Layout.gB

@@ -107,7 +107,7 @@ struct Pipe {
   // The soccer bank pipeline (a second stream beside the live step, MGX_BANK_STREAM): the bank
   // slots' own solver-list state — counter block, histogram, bucket list with stride N * R, arrival
   // lists. The "bank view" of a pipe is a copy whose o_ctr, o_hist, o_blist, o_k2list, o_k2big and
-  // S name this state (mgx_api.hip: bank_view); all per-slot storage keeps its global slot index, so
+  // S name this state (mgx_soccer.hip: bank_view); all per-slot storage keeps its global slot index, so
   // the row builder, sorted_slot, split_count and k_pgs_groups run on either view.
   // o_bstg: per bank record, 1 while the record's rows of this step are staged and its settle step
   // is still to be finished (the row builder sets it, a restart of the record clears it): the bank

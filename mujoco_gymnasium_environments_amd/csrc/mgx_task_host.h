@@ -1,4 +1,4 @@
-// mgx_task_host.h — the host path the seven tasks' C-ABI entries share (mgx_api.hip: soccer;
+// mgx_task_host.h — the host path the seven tasks' C-ABI entries share (mgx_soccer.hip;
 // mgx_parkour.hip, mgx_bipedal.hip, mgx_dancing.hip, mgx_martial.hip, mgx_assembly.hip,
 // mgx_construction.hip): what a step / reset / logic-test call is refused for, in one order and with
 // one set of messages, and the precision x rows-in-scratch choice of the kernel to launch, made from

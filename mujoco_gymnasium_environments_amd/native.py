@@ -17,8 +17,8 @@ ROOT = os.path.dirname(PKG)
 # MGX_LIB: load another build of the same sources (A/B measurements of a kernel variant)
 LIB_PATH = os.environ.get("MGX_LIB") or os.path.join(PKG, "libmgx.so")
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["mgx_api.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip", "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip",
-           "mgx_dancing.hip",
+SOURCES = ["mgx_api.hip", "mgx_staged_host.hip", "mgx_soccer.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip",
+           "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip", "mgx_dancing.hip",
            "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip", "mgx_dyn.hip", "mgx_fd.hip",
            "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip", "mgx_manifold.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)

@@ -43,6 +43,8 @@ class _LdsRows:
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])
 def test_wide_solver_launch_bit_identical(soccer_model, prec):
+    """Under the default split threshold the slots over the hook's 16 rows go to the row-split waves,
+    which this test pins; test_wide_and_single_launch_bit_identical reaches the wide launch."""
     from mujoco_gymnasium_environments_amd.envs.soccer import EFC_CAPACITY, SoccerVectorEnv
     n, steps = 64, 30
     a = SoccerVectorEnv(n, precision=prec, seed=21, full_capacity=True)
@@ -82,6 +84,48 @@ class _Env:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+_WIDE = {"MGX_PGS_SPLIT_BLOCKS": "0", "MGX_PGS_LDS_ROWS": "16"}
+
+
+@pytest.mark.parametrize("hooks,prec", [
+    pytest.param(_WIDE, "f64", id="wide-side-f64"),
+    pytest.param(_WIDE, "f32", id="wide-side-f32"),
+    pytest.param({**_WIDE, "MGX_SIDE_STREAM": "0"}, "f64", id="wide-seq"),
+    pytest.param({**_WIDE, "MGX_PGS_WIDE_LDS": "0"}, "f64", id="wide-globalB"),
+    pytest.param({"MGX_PGS_SPLIT_BLOCKS": "0", "MGX_PGS_SINGLE": "1"}, "f64", id="single"),
+])
+def test_wide_and_single_launch_bit_identical(soccer_model, hooks, prec):
+    """The host branches of the soccer step that the row-split default leaves dormant, each against
+    an env with no hook set, bit for bit over 40 steps (3 banks, same-step autoreset): without split
+    waves, 16 LDS rows send most slots to the wide launch, which runs on the side stream beside the
+    main launch (wide-side), after it on the caller's stream (wide-seq), or with B read from global
+    memory (wide-globalB); MGX_PGS_SINGLE=1 is the one main launch over every slot (single). The
+    wide ids also read the pipe's counters: the wide launch had the listed slots, split mode none."""
+    from mujoco_gymnasium_environments_amd.envs.soccer import SoccerVectorEnv
+    from tests.test_gpu_pgs_split import _counters
+    n, steps = 16, 40
+    a = SoccerVectorEnv(n, precision=prec, seed=71, banks=3, full_capacity=True)
+    with _Env(**hooks):  # read when b's model is created
+        b = SoccerVectorEnv(n, precision=prec, seed=71, banks=3, full_capacity=True)
+    a.reset()
+    b.reset()
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(13)
+    for t in range(steps):
+        act = torch.rand(n, soccer_model.nu, device="cuda:0", generator=g) * 300 - 150
+        ra = a.step(act)
+        rb = b.step(act)
+        torch.cuda.synchronize()
+        for x, y, name in zip(ra[:4], rb[:4], ("obs", "reward", "terminated", "truncated")):
+            assert torch.equal(x, y), (t, name)
+        assert torch.equal(a.batch.qpos, b.batch.qpos) and torch.equal(a.batch.qvel, b.batch.qvel), t
+    if "MGX_PGS_LDS_ROWS" in hooks:
+        split, listed, capE = _counters(b)
+        assert capE == 16
+        assert listed > 20 * n, listed  # the wide launch really had work
+        assert split == 0, split
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])

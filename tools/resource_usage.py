@@ -5,10 +5,10 @@ import sys
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# usage: resource_usage.py [source.hip] [extra hipcc flags]; default mgx_api.hip; mgx_pgs.hip gets
+# usage: resource_usage.py [source.hip] [extra hipcc flags]; default mgx_soccer.hip; mgx_pgs.hip gets
 # its own per-TU flags (native.SOURCE_FLAGS)
 args = sys.argv[1:]
-name = args.pop(0) if args and args[0].endswith(".hip") else "mgx_api.hip"
+name = args.pop(0) if args and args[0].endswith(".hip") else "mgx_soccer.hip"
 src = os.path.join(ROOT, "mujoco_gymnasium_environments_amd", "csrc", name)
 sys.path.insert(0, ROOT)
 from mujoco_gymnasium_environments_amd.native import SOURCE_FLAGS  # noqa: E402

@@ -169,7 +169,7 @@ def main():
         env.step(acts[k % 4])
     torch.cuda.synchronize()
     assert L.mgx_prof_set_buffer(C.c_void_p(buf.data_ptr())) == 0
-    if staged:  # the staged kernels live in their own translation unit (mgx_pgs.hip)
+    if staged:  # mgx_prof_set_buffer is mgx_soccer.hip's (the monolithic kernels); the staged kernels' unit is mgx_pgs.hip
         L.mgx_prof_set_buffer_pgs.argtypes = [C.c_void_p]
         assert L.mgx_prof_set_buffer_pgs(C.c_void_p(buf.data_ptr())) == 0
     for k in range(steps):

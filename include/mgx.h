@@ -968,8 +968,8 @@ int mgx_ik(const mgx_model *m, const mgx_state *state, int n_point, const int32_
  * As above: rows of envs that env_mask deselects are left untouched, every byte of a selected env's
  * non-NULL outputs is written, and the call is asynchronous on the stream and neither allocates
  * nor synchronises.
- * Not provided: sensor derivatives (MuJoCo's C and D), analytic derivatives (mjd_smooth_vel) and
- * derivatives of a task's reward or observation. */
+ * Sensor derivatives (MuJoCo's C and D) are mgx_sensor_fd below. Not provided: analytic
+ * derivatives (mjd_smooth_vel) and derivatives of a task's reward or observation. */
 #define MGX_FD_CENTERED 1
 
 typedef struct mgx_fd_io {
@@ -996,6 +996,57 @@ int64_t mgx_transition_fd_bytes(const mgx_model *m, int slots);
  * returns MGX_OK and launches nothing. */
 int mgx_transition_fd(const mgx_model *m, const mgx_state *state, const mgx_fd_io *io, int n_env,
                       const uint8_t *env_mask, void *stream);
+
+/* ---- finite-difference sensor derivatives (the C and D of MuJoCo's mjd_transitionFD [ext]) ---- */
+/* s(x, u) is the sensordata row of the CURRENT state: what mgx_forward + mgx_sensor give at qpos,
+ * qvel, ctrl and the applied forces, the solver warm-started from qacc_warmstart, nothing written.
+ * With ns = nsensordata,
+ *   C = ds/dx    [N][ns][2nv]
+ *   D = ds/dctrl [N][ns][nu]
+ *   sensordata   [N][ns], the nominal row (that of the clamped nominal ctrl, below),
+ * row-major in the model's real type T. The columns, the perturbations and the control-limit rule
+ * are those of mgx_transition_fd, word for word: tangent columns k < nv go through mj_integratePos
+ * (quaternions turned in double), qvel columns nv <= k < 2nv, ctrl columns 2nv + u against the
+ * nominal ctrl clamped to actuator_ctrlrange, with forward mode's fallback to -eps and then to a
+ * zero column and, under MGX_FD_CENTERED, both sides where both stay inside, else the one that
+ * does. Every entry is (s_a - s_b) / step: one subtraction and one true division in T by the signed
+ * step taken (centred with both sides: by 2 eps). The four rows of a framequat sensor are plain
+ * component differences, as MuJoCo differences sensordata; which of q / -q a sensor reports is the
+ * caller's concern.
+ * No step is taken: the sensors are evaluated at the perturbed current states. MuJoCo's
+ * mjd_transitionFD differences the sensordata that mj_step computed before integrating, so for
+ * one mj_step these are believed to be MuJoCo's C and D (unpinned, as the sensors themselves are).
+ * With D == NULL the ctrl columns take no part: an env then costs 1 + 2nv virtual envs (centred
+ * 1 + 4nv), else 1 + 2nv + nu (centred 1 + 2 (2nv + nu)).
+ * A model whose nsensordata is 0 returns MGX_OK and launches nothing; a model without
+ * mgx_sensor_configure returns MGX_E_ARG. Whatever mgx_forward / mgx_sensor refuse (more than 64
+ * dofs, elliptic cones where an acceleration-stage sensor needs the forward pass, unsupported
+ * sensor types) is refused with their code and message before anything is launched.
+ * As above: nothing in the caller's mgx_state is written; rows of envs that env_mask deselects are
+ * left untouched and every byte of a selected env's non-NULL outputs is written; the call is
+ * asynchronous on the one stream, neither allocates nor synchronises, uses no atomics and is
+ * bit-reproducible.
+ * Not provided: derivatives of the sensors after the step (compose C with mgx_transition_fd's A),
+ * a per-stage sensor subset, sensor noise, analytic derivatives. */
+typedef struct mgx_sensor_fd_io {
+  double eps;                    /* > 0; used in the model's real type */
+  int32_t flags, slots;          /* MGX_FD_CENTERED; virtual envs the workspace holds */
+  void *C, *D, *sensordata;      /* [N][ns][2nv], [N][ns][nu], [N][ns]; each nullable */
+  void *workspace;               /* device memory, mgx_sensor_fd_bytes(m, slots) bytes */
+  uint64_t workspace_bytes;
+} mgx_sensor_fd_io;
+
+/* The workspace holds `slots` virtual envs: what mgx_transition_fd's holds per slot (a complete
+ * mgx_state, the step taken, the mask, the solver scratch) plus the buffers of an mgx_forward_out
+ * and one sensordata staging row; its contents need no initialisation. The call processes
+ * floor(slots / C_virtual) envs per pass and loops on the host. Needs mgx_sensor_configure. */
+int64_t mgx_sensor_fd_bytes(const mgx_model *m, int slots);
+
+/* MGX_E_ARG for slots below one env's virtual envs, eps <= 0, unknown flag bits, a NULL state or
+ * io, or a workspace smaller than mgx_sensor_fd_bytes(m, slots). With no output requested the
+ * call returns MGX_OK and launches nothing. */
+int mgx_sensor_fd(const mgx_model *m, const mgx_state *state, const mgx_sensor_fd_io *io, int n_env,
+                  const uint8_t *env_mask, void *stream);
 
 /* ---- open-loop rollouts (MuJoCo's mujoco.rollout [ext]) --------------------------------------- */
 /* From each env's state, n_roll = K rollouts of n_step = T recorded steps under given control

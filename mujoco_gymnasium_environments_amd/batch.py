@@ -20,6 +20,7 @@ from .ilqr import IlqrMethods
 from .rays import RayMethods
 from .render import RenderMethods
 from .sensors import SensorMethods
+from .sensor_fd import SensorFdMethods
 from .manifold import ManifoldMethods
 from .rollouts import RolloutMethods
 from .transitions import TransitionMethods
@@ -66,7 +67,7 @@ class NativeModel:
 
 
 class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods,
-                   ManifoldMethods, IlqrMethods):
+                   ManifoldMethods, IlqrMethods, SensorFdMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

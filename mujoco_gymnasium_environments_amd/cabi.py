@@ -327,6 +327,11 @@ class MgxFdIO(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64), ("slots", C.c_int32), ("pad0", C.c_int32)]
 
 
+class MgxSensorFdIO(C.Structure):
+    _fields_ = [("eps", C.c_double), ("flags", C.c_int32), ("slots", C.c_int32), ("C", C.c_void_p), ("D", C.c_void_p),
+                ("sensordata", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
 MGX_ROLLOUT_SHARED_CTRL = 1  # include/mgx.h mgx_rollout_io.flags
 
 

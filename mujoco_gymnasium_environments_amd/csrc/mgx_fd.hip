@@ -10,10 +10,17 @@
 //   mgx_step     on the workspace's mgx_state, nsub substeps, no frames;
 //   k_fd_diff    one workgroup per env: differences in the tangent space and transposes
 //                (virtual env = column, dof = row) through an LDS tile into row-major A and B.
+// mgx_sensor_fd_bytes, mgx_sensor_fd are the other half of mjd_transitionFD, the
+// sensor derivatives C and D: the same k_fd_expand, then no step but
+//   mgx_forward  on the virtual envs, where an acceleration-stage sensor needs it;
+//   mgx_sensor   into one staging row per virtual env;
+//   k_sens_diff  one workgroup per env and column tile: plain differences of the staging rows, transposed
+//                (virtual env = column, sensordata entry = row) through the same LDS tile.
 // No atomics anywhere: results are bit-reproducible.
 #include "mgx_internal.h"
 #include "mgx_fd.h"
 #include "mgx_manifold.h"
+#include "mgx_sensor.h"
 
 using namespace mgx;
 
@@ -184,6 +191,68 @@ __global__ void __launch_bounds__(256) k_fd_diff(DevModel<T> m, FdBuf<T> w, int 
   if (w.next_qvel) for (int k = tid; k < nv; k += 256) w.next_qvel[(size_t)env * nv + k] = w.qvel[base * nv + k];
 }
 
+// ------------------------------------------------------------------ sensor difference
+// One workgroup of 4 waves per env and column tile (blockIdx.y; a pass is some tens of envs, so the
+// column tiles are what fills the device), the transposing tile of k_fd_diff: the input's contiguous
+// index is the sensordata entry of one virtual env, the output's the column (a virtual env). Tiles
+// of MGX_FD_TILE columns x MGX_FD_TILE rows are read with lane = sensordata row (coalesced along
+// the staging row), go through LDS (row pitch padded by one real) and are stored with lane = column
+// (coalesced along C's / D's rows); the workgroup loops over the row tiles. Rows are plain
+// differences: a framequat's four components included. Every virtual env of a selected env holds a
+// state (the nominal one where no step was taken), so its staging row is read before the step
+// decides what to do with it: the loads of a tile do not wait for one another. The nominal row goes
+// to `sensordata` (column tile 0).
+template <typename T>
+__global__ void __launch_bounds__(256) k_sens_diff(SensFdBuf<T> w, int e0, int C, int K, int centered, T eps,
+                                                   const uint8_t* mask) {
+  __shared__ T tile[MGX_FD_TILE * (MGX_FD_TILE + 1)];
+  const int env = e0 + blockIdx.x;
+  if (mask && !mask[env]) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ns = w.ns, nu = w.nu, nx2 = 2 * w.nv;
+  const size_t base = (size_t)blockIdx.x * C;
+  const T eps2 = (T)2 * eps;
+  const int c0 = blockIdx.y * MGX_FD_TILE;
+  // a tile of C only, or of D only, whose output is not wanted (uniform over the workgroup)
+  const bool skip = (!w.C && c0 + MGX_FD_TILE <= nx2) || (!w.D && c0 >= nx2);
+  if ((w.C || w.D) && !skip) {
+    for (int r0 = 0; r0 < ns; r0 += MGX_FD_TILE) {
+      const int r = r0 + lane;
+      const T s0 = r < ns ? w.sens[base * ns + r] : (T)0;  // the nominal row's entry
+      __syncthreads();
+      for (int cc = wave; cc < MGX_FD_TILE; cc += 4) {
+        const int c = c0 + cc;
+        T val = 0;
+        if (r < ns && c < K) {
+          const size_t vp = base + 1 + c;
+          const T hp = w.step[vp], sp = w.sens[vp * ns + r];
+          if (!centered) {
+            if (hp != 0) val = (sp - s0) / hp;
+          } else {
+            const size_t vm = vp + K;
+            const T hm = w.step[vm], sm = w.sens[vm * ns + r];
+            if (hp != 0 && hm != 0) val = (sp - sm) / eps2;
+            else if (hp != 0) val = (sp - s0) / hp;
+            else if (hm != 0) val = (sm - s0) / hm;
+          }
+        }
+        tile[lane * (MGX_FD_TILE + 1) + cc] = val;
+      }
+      __syncthreads();
+      for (int rr = wave; rr < MGX_FD_TILE; rr += 4) {
+        const int ro = r0 + rr, c = c0 + lane;
+        if (ro < ns && c < K) {
+          const T val = tile[rr * (MGX_FD_TILE + 1) + lane];
+          if (c < nx2) { if (w.C) w.C[((size_t)env * ns + ro) * nx2 + c] = val; }
+          else if (w.D) w.D[((size_t)env * ns + ro) * nu + (c - nx2)] = val;
+        }
+      }
+    }
+  }
+  if (w.sensordata && blockIdx.y == 0)
+    for (int k = tid; k < ns; k += 256) w.sensordata[(size_t)env * ns + k] = w.sens[base * ns + k];
+}
+
 struct FdDims { int nq, nv, nu, nbody, real_bytes; size_t scratch; };
 
 int fd_dims(const mgx_model* m, FdDims* d) {
@@ -224,9 +293,111 @@ int run_fd(const mgx_model* m, const DevModel<T>& M, const FdDims& d, const mgx_
   return MGX_OK;
 }
 
+struct SensFdDims { FdDims d; int max_ncon, nsd; };
+
+// Dimensions, and what mgx_forward / mgx_sensor would refuse, before anything is launched
+int sens_fd_dims(const mgx_model* m, SensFdDims* sd) {
+  int rc = fd_dims(m, &sd->d);
+  if (rc) return rc;
+  if (!m->sensor) return host_fail(MGX_E_ARG, "mgx_sensor_configure has not been called for this model");
+  if (m->sensor->unsupported) return host_fail(MGX_E_UNSUPPORTED, m->sensor->why);
+  mgx_model_info info;
+  rc = mgx_model_get_info(m, &info);
+  if (rc) return rc;
+  sd->max_ncon = info.max_ncon;
+  sd->nsd = m->sensor->nsensordata;
+  if (sd->nsd > 0 && m->sensor->need_acc) {
+    if (m->wide) return host_fail(MGX_E_UNSUPPORTED, std::string("mgx_forward: ") + MGX_WIDE_MSG);
+    if ((m->precision == MGX_F32 ? m->mf.cone : m->md.cone) != 0)
+      return host_fail(MGX_E_UNSUPPORTED, "mgx_forward decodes pyramidal cones only");
+  }
+  return MGX_OK;
+}
+
+SensFdLayout sens_layout_of(const SensFdDims& sd, int slots) {
+  const FdDims& d = sd.d;
+  return sens_fd_layout(d.nq, d.nv, d.nu, d.nbody, d.real_bytes, d.scratch, sd.max_ncon, sd.nsd, slots);
+}
+
+template <typename T>
+int run_sensor_fd(const mgx_model* m, const DevModel<T>& M, const SensFdDims& sd, const mgx_state* s,
+                  const mgx_sensor_fd_io* io, int n_env, const uint8_t* mask, hipStream_t st) {
+  const FdDims& d = sd.d;
+  // the ctrl columns are the last ones: without D the expand kernel stops before them
+  const int K = 2 * d.nv + (io->D ? d.nu : 0), centered = io->flags & MGX_FD_CENTERED ? 1 : 0, C = 1 + (centered ? 2 : 1) * K;
+  const SensFdLayout L = sens_layout_of(sd, io->slots);
+  const FdLayout& o = L.fd;
+  char* ws = (char*)io->workspace;
+  FdBuf<T> w{(T*)(ws + o.qpos), (T*)(ws + o.qvel), (T*)(ws + o.qacc), (T*)(ws + o.ctrl), (T*)(ws + o.qfrc),
+             (T*)(ws + o.xfrc), (T*)(ws + o.time), (T*)(ws + o.step), (int32_t*)(ws + o.warning),
+             (int32_t*)(ws + o.overflow), (uint8_t*)(ws + o.vmask), nullptr, nullptr, nullptr, nullptr, nullptr};
+  mgx_state vs{};
+  vs.qpos = w.qpos; vs.qvel = w.qvel; vs.qacc_warmstart = w.qacc; vs.ctrl = w.ctrl; vs.qfrc_applied = w.qfrc;
+  vs.xfrc_applied = w.xfrc; vs.time = w.time; vs.warning = w.warning; vs.overflow = w.overflow;
+  vs.scratch = d.scratch ? ws + o.scratch : nullptr;
+  mgx_forward_out fo{};
+  fo.qacc = ws + L.f_qacc; fo.qfrc_constraint = ws + L.f_qfrc; fo.ncon = (int32_t*)(ws + L.f_ncon);
+  fo.con_geom = (int32_t*)(ws + L.f_geom); fo.con_dist = ws + L.f_dist; fo.con_pos = ws + L.f_pos;
+  fo.con_frame = ws + L.f_frame; fo.con_force = ws + L.f_force;
+  const bool need_fwd = m->sensor->need_acc;
+  SensFdBuf<T> b{(const T*)(ws + L.sens), w.step, (T*)io->C, (T*)io->D, (T*)io->sensordata, sd.nsd, d.nv, d.nu};
+  const int per = io->slots / C;  // envs per pass
+  const T eps = (T)io->eps;
+  for (int e0 = 0; e0 < n_env; e0 += per) {
+    const int cnt = n_env - e0 < per ? n_env - e0 : per;
+    hipLaunchKernelGGL(k_fd_expand<T>, dim3(cnt * C), dim3(64), 0, st, M, *s, w, e0, C, K, centered, eps, mask);
+    MGX_HIPCHK(hipGetLastError());
+    // the library's own forward pass and sensor kernel, exactly as a caller of mgx_forward and
+    // mgx_sensor gets them; virtual envs of deselected envs hold no state and are masked out
+    const uint8_t* vmask = mask ? w.vmask : nullptr;
+    int rc;
+    if (need_fwd) {
+      rc = mgx_forward(m, &vs, &fo, cnt * C, vmask, st);
+      if (rc) return rc;
+    }
+    rc = mgx_sensor(m, &vs, need_fwd ? &fo : nullptr, ws + L.sens, cnt * C, vmask, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sens_diff<T>, dim3(cnt, K > 0 ? (K + MGX_FD_TILE - 1) / MGX_FD_TILE : 1), dim3(256), 0, st, b, e0, C, K, centered,
+                       eps, mask);
+    MGX_HIPCHK(hipGetLastError());
+  }
+  return MGX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t mgx_sensor_fd_bytes(const mgx_model* m, int slots) {
+  if (!m || slots < 1) return host_fail(MGX_E_ARG, "null model or slots < 1");
+  SensFdDims sd;
+  const int rc = sens_fd_dims(m, &sd);
+  if (rc) return rc;
+  return (int64_t)sens_layout_of(sd, slots).bytes;
+}
+
+int mgx_sensor_fd(const mgx_model* m, const mgx_state* s, const mgx_sensor_fd_io* io, int n_env, const uint8_t* env_mask,
+                  void* stream) {
+  if (!m || !io || n_env < 0) return host_fail(MGX_E_ARG, "null argument or n_env < 0");
+  int rc = host_check_state(s);
+  if (rc) return rc;
+  if (io->flags & ~MGX_FD_CENTERED) return host_fail(MGX_E_ARG, "unknown mgx_sensor_fd_io.flags bits");
+  if (!(io->eps > 0)) return host_fail(MGX_E_ARG, "eps must be > 0");
+  SensFdDims sd;
+  rc = sens_fd_dims(m, &sd);
+  if (rc) return rc;
+  if (sd.nsd == 0) return MGX_OK;  // a model without sensors: nothing to launch
+  const FdDims& d = sd.d;
+  const int K = 2 * d.nv + (io->D ? d.nu : 0), C = 1 + (io->flags & MGX_FD_CENTERED ? 2 : 1) * K;
+  if (io->slots < C)
+    return host_fail(MGX_E_ARG, "slots below the virtual envs of one env (1 + K, centred 1 + 2 K; K = 2 nv + nu, without D 2 nv)");
+  if (!io->workspace || io->workspace_bytes < sens_layout_of(sd, io->slots).bytes)
+    return host_fail(MGX_E_ARG, "workspace smaller than mgx_sensor_fd_bytes");
+  if (n_env == 0 || (!io->C && !io->D && !io->sensordata)) return MGX_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (m->precision == MGX_F32) return run_sensor_fd<float>(m, m->mf, sd, s, io, n_env, env_mask, st);
+  return run_sensor_fd<double>(m, m->md, sd, s, io, n_env, env_mask, st);
+}
 
 int64_t mgx_transition_fd_bytes(const mgx_model* m, int slots) {
   if (!m || slots < 1) return host_fail(MGX_E_ARG, "null model or slots < 1");

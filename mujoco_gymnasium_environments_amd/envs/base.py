@@ -27,6 +27,7 @@ from ..manifold import ManifoldForwarding
 from ..rollouts import RolloutForwarding
 from ..seeding import np_random
 from ..sensors import SensorForwarding
+from ..sensor_fd import SensorFdForwarding
 from ..spaces import EnvBase, policy_action
 from ..transitions import TransitionForwarding
 
@@ -42,7 +43,7 @@ def device_actions(actions: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, IkForwarding, TransitionForwarding,
-                    RolloutForwarding, ManifoldForwarding, IlqrForwarding):
+                    RolloutForwarding, ManifoldForwarding, IlqrForwarding, SensorFdForwarding):
     """``num_envs`` envs of one task stepping in lockstep on one GPU, one fused launch (or one
     staged pipeline) per env step, with same-step autoreset."""
 

@@ -288,6 +288,24 @@ class StreamShardedEnv:
                                          out=full.rows(a, b), **kw)
         return TransitionResult(**{f: getattr(full, f) for f in FD_OUTPUTS if getattr(part, f) is not None})
 
+    def sensor_fd(self, mask: Optional[torch.Tensor] = None, stream=None, only=None, **kw):
+        """PhysicsBatch.sensor_fd over every shard, into slices of one set of tensors."""
+        from ..sensor_fd import SENSOR_FD_OUTPUTS, SensorFdResult, alloc_sensor_fd
+        cs = stream if stream is not None else torch.cuda.current_stream(self.device)
+        full = self.__dict__.get("_sensor_fd_out")
+        if full is None:
+            b0, m = self.shards[0].batch, self.model
+            full = self._sensor_fd_out = alloc_sensor_fd(self.num_envs, int(m.nsensordata), int(m.nv), int(m.nu),
+                                                         b0.dtype, self.device)
+        part = None
+        for (a, b), s in zip(self.bounds, self.shards):
+            part = s.batch.sensor_fd(mask=None if mask is None else mask[a:b], stream=cs, only=only,
+                                     out=full.rows(a, b), **kw)
+        return SensorFdResult(**{f: getattr(full, f) for f in SENSOR_FD_OUTPUTS if getattr(part, f) is not None})
+
+    def sensor_fd_columns(self, centered: bool = False, with_d: bool = True) -> int:
+        return self.shards[0].batch.sensor_fd_columns(centered, with_d)
+
     @property
     def state_size(self) -> int:
         return self.shards[0].batch.state_size

@@ -18,8 +18,20 @@ The cost is the diagonal quadratic
 
 and its derivatives take d(dx)/dx = I: the Gauss-Newton form, exact for models without quaternion
 joints and near the goal (the Jacobian of the rotation-vector difference is I + O(|dx|)).
-Not provided: any other cost, constraints beyond the control clamp of ``rollout_feedback``,
-box-DDP and sensor derivatives.
+
+With ``sensor_goal`` / ``w_s`` / ``w_sf`` the cost adds a residual on the sensors,
+
+    sum_{t=1..T-1} 1/2 r_t' diag(w_s) r_t + 1/2 r_T' diag(w_sf) r_T,   r_t = s(x_t) - s*_t,
+
+x_t the state after recorded step t (x_0 is fixed: its term is a constant and is left out) and s the
+``sensordata()`` row. The line search reads r_t from the closed-loop rollout's own ``sensordata``
+output; the backward pass takes the Gauss-Newton terms ``C_t' (w o r_t)`` and ``C_t' diag(w) C_t``
+with ``C_t = ds/dx`` from ``sensor_fd_along`` at the trajectory's states (``only=("C",)``: no ctrl
+columns). Rows of accelerometer, force, torque and touch sensors may not be weighted: they read
+``ctrl`` and the solver, so a cost on them couples x_{t+1} with u_t, which this backward pass does
+not model (and the rollout records them with the ctrl of the step that led to x_t).
+Not provided: any other cost, costs on acceleration-stage sensors, constraints beyond the control
+clamp of ``rollout_feedback`` and box-DDP.
 """
 from __future__ import annotations
 
@@ -88,11 +100,15 @@ def lqr_backward(A, B, lx, lxx, lu, luu, lux, Vx_T, Vxx_T, mu):
 
 class IlqrProblem:
     """x0 [N, nstate] (the start), goal [N, nstate] or [N, T + 1, nstate], the horizon T, the
-    weights w_x, w_xf [2nv] and w_u [nu] (each [n] or [N, n]) and u_init [N, T, nu] (None: zeros)."""
+    weights w_x, w_xf [2nv] and w_u [nu] (each [n] or [N, n]) and u_init [N, T, nu] (None: zeros).
+    The sensor residual: sensor_goal [N, ns] or [N, T, ns] (row t - 1 is s*_t, the goal of the state
+    after recorded step t) and the weights w_s, w_sf [ns] or [N, ns] (None: zeros); all three None:
+    no sensor cost."""
 
-    def __init__(self, x0, goal, horizon, w_x, w_xf, w_u, u_init=None):
+    def __init__(self, x0, goal, horizon, w_x, w_xf, w_u, u_init=None, sensor_goal=None, w_s=None, w_sf=None):
         self.x0, self.goal, self.horizon = x0, goal, int(horizon)
         self.w_x, self.w_xf, self.w_u, self.u_init = w_x, w_xf, w_u, u_init
+        self.sensor_goal, self.w_s, self.w_sf = sensor_goal, w_s, w_sf
 
 
 def trajectory_cost(system, problem, state, ctrl, w):
@@ -108,6 +124,43 @@ def trajectory_cost(system, problem, state, ctrl, w):
     w_x, w_xf, w_u = (lead(x) for x in w)
     run = 0.5 * (w_x * dx[..., :T, :] ** 2).sum((-1, -2)) + 0.5 * (w_u * ctrl ** 2).sum((-1, -2))
     return run + 0.5 * (w_xf[..., 0, :] * dx[..., T, :] ** 2).sum(-1), dx
+
+
+ACC_SENSOR_TYPES = ("accelerometer", "force", "torque", "touch")
+
+
+def sensor_weights(model, problem, N, dtype, device):
+    """(sensor_goal [N, 1 | T, ns], w_s [N, ns], w_sf [N, ns]) of a problem with a sensor cost.
+    ValueError for a nonzero weight on a row of an acceleration-stage sensor, naming the sensor."""
+    from .mjcf import SENSOR_TYPES
+    ns, T = int(model.nsensordata), problem.horizon
+    if problem.sensor_goal is None:
+        raise ValueError("w_s / w_sf need a sensor_goal")
+    goal = torch.as_tensor(problem.sensor_goal, dtype=dtype, device=device)
+    if tuple(goal.shape) == (N, ns):
+        goal = goal[:, None, :]
+    elif tuple(goal.shape) != (N, T, ns):
+        raise ValueError(f"sensor_goal must be [N, ns] or [N, T, ns] = {[N, T, ns]}, got {tuple(goal.shape)}")
+    zero = torch.zeros(ns, dtype=dtype, device=device)
+    w_s, w_sf = (torch.as_tensor(zero if x is None else x, dtype=dtype, device=device).expand(N, ns).contiguous()
+                 for x in (problem.w_s, problem.w_sf))
+    used = ((w_s != 0) | (w_sf != 0)).any(0).cpu()
+    for name, typ, adr, dim in zip(model.sensor_names, model.sensor_type, model.sensor_adr, model.sensor_dim):
+        if SENSOR_TYPES[int(typ)] in ACC_SENSOR_TYPES and bool(used[int(adr):int(adr) + int(dim)].any()):
+            raise ValueError(f"sensor {name!r} ({SENSOR_TYPES[int(typ)]}) reads ctrl and the solver: a cost on it "
+                             f"couples x_(t+1) with u_t, which the backward pass does not model; its weights must be 0")
+    return goal, w_s, w_sf
+
+
+def sensor_cost(sens, sw):
+    """(J_s [..], r [N, ..., T, ns]) of recorded sensordata sens [N, ..., T, ns] (row t - 1: the
+    sensors at the state after recorded step t); ``sw`` = (goal, w_s, w_sf) of ``sensor_weights``."""
+    goal, w_s, w_sf = sw
+    N, extra = sens.shape[0], sens.dim() - 3
+    lead = lambda x: x.reshape((N,) + (1,) * extra + tuple(x.shape[1:]))  # noqa: E731
+    r = sens - lead(goal)
+    run = 0.5 * (lead(w_s[:, None, :]) * r[..., :-1, :] ** 2).sum((-1, -2))
+    return run + 0.5 * (lead(w_sf) * r[..., -1, :] ** 2).sum(-1), r
 
 
 def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] = DEFAULT_ALPHAS, mu0: float = 1e-6,
@@ -132,7 +185,11 @@ def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] =
     [N, T + 1, nstate], gain [N, T, nu, 2nv], k_ff [N, T, nu], cost [N], cost_history [iters + 1, N],
     iters [N], status [N])``: ``state`` is what ``ctrl`` produces from ``x0`` (the applied, clamped
     control), ``gain`` and ``k_ff`` belong to the last accepted step. Nothing is written to the
-    system's state."""
+    system's state.
+
+    A problem with a sensor cost (module docstring) also needs ``sensor_fd_along``, the
+    ``sensordata`` output of ``rollout_feedback`` and the model's sensor tables; without one none
+    of them is touched and the result is bit for bit that of the plain solve."""
     x0 = problem.x0
     N, T, ns = x0.shape[0], problem.horizon, system.state_size
     nv, nu = int(system.model.nv), int(system.model.nu)
@@ -143,11 +200,18 @@ def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] =
     alpha = torch.tensor([float(a) for a in alphas], dtype=dt, device=dev).repeat(N, 1).contiguous()
     u = torch.zeros(N, T, nu, dtype=dt, device=dev) if problem.u_init is None else problem.u_init.to(dt).contiguous()
     inf = torch.tensor(float("inf"), dtype=dt, device=dev)
+    sw = None
+    if problem.sensor_goal is not None or problem.w_s is not None or problem.w_sf is not None:
+        sw = sensor_weights(system.model, problem, N, dt, dev)
+    rec = dict(sensordata=True) if sw else {}  # the rollouts record the sensors only for a sensor cost
 
-    r = system.rollout_feedback(u, initial_state=x0[:, None, :].contiguous(), nsub=nsub)
+    r = system.rollout_feedback(u, initial_state=x0[:, None, :].contiguous(), nsub=nsub, **rec)
     state = torch.cat([x0[:, None, :], r.state[:, 0]], dim=1)
     ctrl, warm = r.ctrl[:, 0].clone(), r.warmstart[:, 0].clone()
     cost, _ = trajectory_cost(system, problem, state, ctrl, w)
+    if sw:
+        sens = r.sensordata[:, 0].clone()
+        cost = cost + sensor_cost(sens, sw)[0]
     cost = torch.where(r.n_done[:, 0] < T, inf, cost)
     k_ff = torch.zeros(N, T, nu, dtype=dt, device=dev)
     gain = torch.zeros(N, T, nu, 2 * nv, dtype=dt, device=dev)
@@ -184,8 +248,22 @@ def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] =
         lxx = (w[0][:, None, :, None] * eye_x).expand(N, T, 2 * nv, 2 * nv)
         luu = (w[2][:, None, :, None] * eye_u).expand(N, T, nu, nu)
         lux = torch.zeros(N, T, nu, 2 * nv, dtype=dt, device=dev)
+        Vx_T, Vxx_T = w[1] * dx[:, T], w[1][:, :, None] * eye_x
+        if sw:
+            # C at x_1 .. x_T, each with the ctrl of the step that led to it, as the rollout recorded
+            # its sensors (the weighted rows read neither ctrl nor the warm start)
+            Cs = system.sensor_fd_along(state[:, 1:].contiguous(), ctrl, centered=centered, only=("C",)).C
+            res = sensor_cost(sens, sw)[1]
+            CT = Cs.transpose(2, 3)
+            wr = torch.cat([sw[1][:, None, :].expand(N, T - 1, -1), sw[2][:, None, :]], dim=1)  # [N, T, ns]
+            gx = (CT @ (wr * res)[..., None])[..., 0]  # [N, T, 2nv]: row t - 1 belongs to x_t
+            gxx = CT @ (wr[..., None] * Cs)
+            lx, lxx = lx.clone(), lxx.clone()
+            lx[:, 1:] += gx[:, :T - 1]
+            lxx[:, 1:] += gxx[:, :T - 1]
+            Vx_T, Vxx_T = Vx_T + gx[:, T - 1], Vxx_T + gxx[:, T - 1]
         while True:
-            bw = lqr_backward(lin.A, lin.B, lx, lxx, lu, luu, lux, w[1] * dx[:, T], w[1][:, :, None] * eye_x, mu)
+            bw = lqr_backward(lin.A, lin.B, lx, lxx, lu, luu, lux, Vx_T, Vxx_T, mu)
             bad = active & ((bw.info != 0) | ~torch.isfinite(bw.k_ff).all(-1).all(-1))
             if not bool(bad.any()):
                 break
@@ -199,9 +277,11 @@ def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] =
         status = torch.where(done, torch.full_like(status, CONVERGED), status)
         active = active & ~done
         rr = system.rollout_feedback(ctrl, x_nom=state[:, :T].contiguous(), k_ff=new_k, alpha=alpha, gain=new_g,
-                                     initial_state=x0k, initial_warmstart=w0k, nsub=nsub)
+                                     initial_state=x0k, initial_warmstart=w0k, nsub=nsub, **rec)
         cand = torch.cat([x0k[:, :, None, :], rr.state], dim=2)
         costs, _ = trajectory_cost(system, problem, cand, rr.ctrl, w)
+        if sw:
+            costs = costs + sensor_cost(rr.sensordata, sw)[0]
         costs = torch.where((rr.n_done < T) | ~torch.isfinite(costs), inf, costs)
         best_cost, best = costs.min(dim=1)
         accept = active & (best_cost < cost)
@@ -210,6 +290,8 @@ def solve(system, problem: IlqrProblem, nsub: int = 1, alphas: Sequence[float] =
         state = sel(accept, pick(cand), state)
         ctrl = sel(accept, pick(rr.ctrl), ctrl)
         warm = sel(accept, pick(rr.warmstart), warm)
+        if sw:
+            sens = sel(accept, pick(rr.sensordata), sens)
         k_ff, gain = sel(accept, new_k, k_ff), sel(accept, new_g, gain)
         small = accept & ((cost - best_cost) < tol * cost.abs())
         cost = torch.where(accept, best_cost, cost)
@@ -230,13 +312,17 @@ class IlqrMethods:
 
     def solve_ilqr(self, goal_state: torch.Tensor, horizon: int, w_x, w_xf, w_u, u_init: Optional[torch.Tensor] = None,
                    nsub: int = 1, alphas: Sequence[float] = DEFAULT_ALPHAS, mu0: float = 1e-6, mu_factor: float = 10.0,
-                   max_iter: int = 20, tol: float = 1e-6, centered: bool = False) -> IlqrResult:
+                   max_iter: int = 20, tol: float = 1e-6, centered: bool = False, sensor_goal=None, w_s=None,
+                   w_sf=None) -> IlqrResult:
         """``ilqr.solve`` from every env's current state towards ``goal_state`` [N, nstate] or
         [N, T + 1, nstate] over ``horizon`` = T recorded steps of ``nsub`` mj_steps, with the
         diagonal quadratic cost of :mod:`~.ilqr` (weights [n] or [N, n]; the Gauss-Newton gradient
-        takes d(dx)/dx = I). See ``ilqr.solve`` for the iteration and the result. The batch's
-        state is not written."""
-        problem = IlqrProblem(self.get_state(), goal_state.to(self.dtype), horizon, w_x, w_xf, w_u, u_init)
+        takes d(dx)/dx = I) and, with ``sensor_goal`` [N, ns] or [N, T, ns] and the weights ``w_s``,
+        ``w_sf`` ([ns] or [N, ns]), its sensor residual (``sensor_slices`` maps names to rows;
+        accelerometer, force, torque and touch rows may not be weighted). See ``ilqr.solve`` for
+        the iteration and the result. The batch's state is not written."""
+        problem = IlqrProblem(self.get_state(), goal_state.to(self.dtype), horizon, w_x, w_xf, w_u, u_init,
+                              sensor_goal=sensor_goal, w_s=w_s, w_sf=w_sf)
         return solve(self, problem, nsub=nsub, alphas=alphas, mu0=mu0, mu_factor=mu_factor, max_iter=max_iter, tol=tol,
                      centered=centered)
 

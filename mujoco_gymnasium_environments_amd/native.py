@@ -30,7 +30,7 @@ HEADERS = ["mgx_common.h", "mgx_collide.h", "mgx_physics.h", "mgx_soccer.h", "mg
 # task headers included by one translation unit only (so editing one rebuilds one object)
 TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_sensor.h"], "mgx_dyn.hip": ["mgx_dyn.h"],
               "mgx_ik.hip": ["mgx_ik.h", "mgx_dyn.h"],
-              "mgx_fd.hip": ["mgx_fd.h", "mgx_manifold.h"],
+              "mgx_fd.hip": ["mgx_fd.h", "mgx_manifold.h", "mgx_sensor.h"],
               "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h", "mgx_manifold.h"], "mgx_manifold.hip": ["mgx_manifold.h"],
               "mgx_render.hip": ["mgx_render.h"]}
 
@@ -198,6 +198,8 @@ _SIGS = {
                C.c_int),
     "mgx_transition_fd_bytes": ([_VP, C.c_int], C.c_int64),
     "mgx_transition_fd": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxFdIO), C.c_int, _VP, _VP], C.c_int),
+    "mgx_sensor_fd_bytes": ([_VP, C.c_int], C.c_int64),
+    "mgx_sensor_fd": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxSensorFdIO), C.c_int, _VP, _VP], C.c_int),
     "mgx_rollout_bytes": ([_VP, C.c_int, C.c_int], C.c_int64),
     "mgx_rollout": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxRolloutIO), C.c_int, _VP, _VP], C.c_int),
     "mgx_state_diff": ([_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP], C.c_int),

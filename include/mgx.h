@@ -1188,6 +1188,64 @@ typedef struct mgx_feedback_io {
 int mgx_rollout_feedback(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io,
                          const mgx_feedback_io *fb, int n_env, const uint8_t *env_mask, void *stream);
 
+/* ---- rollout costs (sampling planners: MPPI, predictive sampling) ------------------------------ */
+/* mgx_rollout_cost is mgx_rollout (fb NULL) or mgx_rollout_feedback (fb given) that also scores
+ * every rollout while it runs, so that a planner which needs cost [N][K] only has to materialise
+ * neither state [N][K][T][nstate] nor sensordata. With x_0 the rollout's initial state, x_t the
+ * state after recorded step t (row t - 1 of the `state` output), T = n_step, v = e K + k:
+ *   J[v] = 1/2 w_x.dx_0^2 + sum_{t=1..T-1} 1/2 w_x.dx_t^2 + 1/2 w_xf.dx_T^2        (terms[v][0])
+ *        + sum_{t=0..T-1} 1/2 w_u.u_t^2                                            (terms[v][1])
+ *        + sum_{t=1..T-1} 1/2 w_s.r_t^2 + 1/2 w_sf.r_T^2                           (terms[v][2])
+ * where w.d^2 = sum_i w[e][i] d[i]^2 and
+ *   dx_t = mgx_state_diff(x_t, goal[e][goal_rows == 1 ? 0 : t]): the T-rounded tangent entries
+ *          (2 nv of them) that entry point returns, bit for bit;
+ *   u_t  = the virtual env's ctrl row as handed to recorded step t: open loop the knot as given
+ *          (not clamped: the clamp is the step's job and is not seen here; with io->ctrl NULL the
+ *          env's current ctrl), with fb what ctrl_out records (clamped under MGX_FEEDBACK_CLAMP);
+ *   r_t  = s(x_t) - sensor_goal[e][sensor_rows == 1 ? 0 : t - 1], one subtraction in T, s(x_t) the
+ *          row t - 1 that the `sensordata` output holds (acceleration-stage sensors included).
+ * Arithmetic: every product 1/2 w d d is formed in double from the T-valued operands w and d as
+ * (0.5 * (double)w) * ((double)d * (double)d), each operation rounded once (no fused multiply-
+ * add), whatever T is. The terms of one step are summed in double over i in a fixed order that
+ * depends on nothing but nv, nu and ns (not specified further) into three partial sums (state,
+ * control, sensor); the one lane that owns v then adds, in step order and in place,
+ * (state + control) + sensor to cost[v] and each part to terms[v][0..2]. So cost[v] equals
+ * terms[v][0] + terms[v][1] + terms[v][2] up to the rounding of these sums, not bit for bit. No
+ * atomics: results are bit-reproducible and do not depend on slots, on which other outputs are
+ * requested (terms included), or on the previous contents of any buffer.
+ * A NULL goal drops the state term, a NULL sensor_goal the sensor term (terms[v][.] = 0); a NULL
+ * weight is all zeros. A rollout that diverges (n_done < T) gets cost = terms[.] = +inf. Rows of
+ * envs that env_mask deselects are left untouched; every byte of a selected env's cost (and terms)
+ * row is written. Nothing in the caller's mgx_state is written. The workspace is that of
+ * mgx_rollout_bytes(m, slots, with_sensors), with_sensors = (io->sensordata or cost->sensor_goal
+ * non-NULL). io->state, io->sensordata and io->n_done may all be NULL: the call still runs.
+ * Launches per pass: one cost-initialising kernel after k_rollout_begin, then per recorded step
+ * one k_rollout_cost after the step and the sensor kernels and before k_rollout_record.
+ * Asynchronous on the one stream, no allocation, no synchronisation (graph-capturable).
+ * Not provided: any other cost shape, cost terms on the applied forces, discounting. */
+typedef struct mgx_cost_io {
+  const void *goal;         /* T [N][goal_rows][nstate]; row t is the goal of x_t; NULL: no state term */
+  const void *w_x, *w_xf;   /* T [N][2nv]; NULL: zeros */
+  const void *w_u;          /* T [N][nu];  NULL: zeros */
+  const void *sensor_goal;  /* T [N][sensor_rows][ns]; row t-1 is the goal of s(x_t); NULL: no sensor term */
+  const void *w_s, *w_sf;   /* T [N][ns];  NULL: zeros */
+  int32_t goal_rows;        /* 1 or n_step + 1 */
+  int32_t sensor_rows;      /* 1 or n_step */
+  int32_t flags, pad0;      /* no bits defined: must be 0 */
+  void *cost;               /* out double [N][K], required */
+  void *terms;              /* out double [N][K][3]: state, control, sensor parts; nullable */
+} mgx_cost_io;
+
+/* MGX_E_ARG, before the model or the state is looked at, for: a NULL io; a NULL cost or
+ * cost->cost; goal_rows not 1 or n_step + 1 with a goal; sensor_rows not 1 or n_step with a
+ * sensor_goal; w_s or w_sf without sensor_goal; w_x or w_xf without goal; nonzero flags. Then, with
+ * fb non-NULL, the checks of mgx_rollout_feedback; then every error of mgx_rollout, the refusals of
+ * mgx_forward included when the sensor term is on (a model of more than 64 dofs, elliptic cones, no
+ * mgx_sensor_configure). */
+int mgx_rollout_cost(const mgx_model *m, const mgx_state *state, const mgx_rollout_io *io,
+                     const mgx_feedback_io *fb /* NULL: open loop */, const mgx_cost_io *cost,
+                     int n_env, const uint8_t *env_mask, void *stream);
+
 /* ---- RGB camera images (ray-traced rgb_array) -------------------------------------------------- */
 /* The colour image of one of the model's cameras for every env, on the primary rays of
  * mgx_ray_camera. This is NOT MuJoCo's OpenGL image: it is the small shading model stated here

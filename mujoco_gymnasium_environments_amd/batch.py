@@ -17,6 +17,7 @@ from .native import MGX_F32, MGX_F64, check, lib
 from .dynamics import DynamicsMethods
 from .ik import IkMethods
 from .ilqr import IlqrMethods
+from .sampling import SamplingMethods
 from .rays import RayMethods
 from .render import RenderMethods
 from .sensors import SensorMethods
@@ -67,7 +68,7 @@ class NativeModel:
 
 
 class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods,
-                   ManifoldMethods, IlqrMethods, SensorFdMethods):
+                   ManifoldMethods, IlqrMethods, SensorFdMethods, SamplingMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

@@ -352,6 +352,13 @@ class MgxFeedbackIO(C.Structure):
                 ("warm_out", C.c_void_p)]
 
 
+class MgxCostIO(C.Structure):  # include/mgx.h mgx_cost_io (mgx_rollout_cost)
+    _fields_ = [("goal", C.c_void_p), ("w_x", C.c_void_p), ("w_xf", C.c_void_p), ("w_u", C.c_void_p),
+                ("sensor_goal", C.c_void_p), ("w_s", C.c_void_p), ("w_sf", C.c_void_p), ("goal_rows", C.c_int32),
+                ("sensor_rows", C.c_int32), ("flags", C.c_int32), ("pad0", C.c_int32), ("cost", C.c_void_p),
+                ("terms", C.c_void_p)]
+
+
 MGX_RENDER_MAX_LAYERS, MGX_RENDER_MAX_LIGHT = 4, 8  # include/mgx.h
 MGX_TEX_2D, MGX_TEX_CUBE, MGX_TEX_SKYBOX = 0, 1, 2  # mjcf.TEX_TYPES
 MGX_BUILTIN_NONE, MGX_BUILTIN_GRADIENT, MGX_BUILTIN_CHECKER, MGX_BUILTIN_FLAT = 0, 1, 2, 3  # mjcf.TEX_BUILTIN

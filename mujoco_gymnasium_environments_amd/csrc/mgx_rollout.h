@@ -62,4 +62,14 @@ struct FeedbackBuf {
   int clamp;
 };
 
+// The cost of mgx_rollout_cost (mgx_cost_io), typed; goals and weights indexed by env e, the two
+// outputs by v. A NULL goal / sgoal drops the term, a NULL weight is zeros.
+template <typename T>
+struct CostBuf {
+  const T *goal, *w_x, *w_xf, *w_u;  // [e][goal_rows][nstate], [e][2nv], [e][2nv], [e][nu]
+  const T *sgoal, *w_s, *w_sf;       // [e][sensor_rows][nsd], [e][nsd], [e][nsd]
+  int goal_rows, sensor_rows;
+  double *cost, *terms;  // [v], [v][3] (nullable)
+};
+
 }  // namespace mgx

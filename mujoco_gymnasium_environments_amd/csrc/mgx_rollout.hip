@@ -1,7 +1,10 @@
 // mgx_rollout.hip — open-loop rollouts (MuJoCo's mujoco.rollout [ext]) and their C-ABI:
 // mgx_rollout_bytes, mgx_rollout (include/mgx.h), and the closed-loop
 // mgx_rollout_feedback, which adds k_rollout_feedback before every mgx_step: the
-// step's ctrl from the virtual env's own state.
+// step's ctrl from the virtual env's own state; and mgx_rollout_cost, either of the
+// two with k_rollout_cost_begin after k_rollout_begin and k_rollout_cost before every
+// k_rollout_record: the rollout's cost accumulated from the workspace, so that no trajectory has to
+// be recorded to score it.
 //
 // Rollout k of env e is virtual env v = e K + k. A pass materialises a range of v in the caller's
 // workspace (the virtual-env workspace of mgx_transition_fd held for T steps instead of one) and
@@ -159,6 +162,94 @@ __global__ void __launch_bounds__(256) k_rollout_feedback(DevModel<T> m, Rollout
   }
 }
 
+// ------------------------------------------------------------------ cost
+// sum_{i < n} 1/2 w[i] d(i)^2 over the wave (mgx_rollout_cost, include/mgx.h): in double from the
+// T-valued operands, every operation rounded once (no contraction into fused multiply-adds). Lane
+// l sums its entries i = l, l + 64, ... in that order, then a butterfly of cross-lane moves in lane
+// order: the order depends on n alone, there are no atomics, and every lane holds the sum.
+template <typename T, typename F>
+__device__ __forceinline__ double wave_half_wsq(const T* w, int n, int l, F d) {
+#pragma clang fp contract(off)
+  double acc = 0;
+  for (int i = l; i < n; i += 64) {
+    const double x = (double)d(i);
+    acc = acc + (0.5 * (double)w[i]) * (x * x);
+  }
+  for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o, 64);
+  return acc;
+}
+
+// 1/2 wx . dx^2 of slot b's state against goal row `row` of its env, dx the entries of mgx_state_diff
+template <typename T>
+__device__ __forceinline__ double cost_state_part(const DevModel<T>& m, const RolloutBuf<T>& w, const CostBuf<T>& c, int b,
+                                                  int env, int row, const T* wx, int l) {
+  if (!c.goal || !wx) return 0;
+  const int nq = w.nq, nv = w.nv;
+  const T* g = c.goal + ((size_t)env * c.goal_rows + (c.goal_rows == 1 ? 0 : row)) * ((size_t)1 + nq + nv);
+  const T* q = w.qpos + (size_t)b * nq;
+  const T* qv = w.qvel + (size_t)b * nv;
+  return wave_half_wsq(wx + (size_t)env * 2 * nv, 2 * nv, l,
+                       [&](int r) { return tangent_delta<true>(tangent_row(m, r), q, qv, g + 1, g + 1 + nq); });
+}
+
+// After k_rollout_begin: the x_0 term. One wave per virtual env; lane 0 is the single writer of
+// cost[v] and terms[v] for the whole call, and here it overwrites whatever they held.
+template <typename T>
+__global__ void __launch_bounds__(64) k_rollout_cost_begin(DevModel<T> m, RolloutBuf<T> w, CostBuf<T> c, int v0) {
+  const int b = blockIdx.x, l = threadIdx.x;
+  if (!__builtin_amdgcn_readfirstlane((int)w.live[b])) return;  // one byte, the same for every lane
+  const int v = v0 + b, env = v / w.K;
+  const double sx = cost_state_part(m, w, c, b, env, 0, c.w_x, l);
+  if (l == 0) {
+    c.cost[v] = sx;
+    if (c.terms) { c.terms[(size_t)v * 3] = sx; c.terms[(size_t)v * 3 + 1] = 0; c.terms[(size_t)v * 3 + 2] = 0; }
+  }
+}
+
+// After recorded step t and its sensor kernels, before k_rollout_record (which loads the next ctrl
+// and clears the live flag of a rollout that diverged): the terms of u_t, x_(t+1) and s(x_(t+1)),
+// read from the workspace. The live flag and the warning count are broadcast as record does it, so
+// the branches are uniform. The K rollouts of an env read the same goal rows and weights: after
+// the first of them they come from L2. A rollout that diverged at this step costs +inf and, no
+// longer live after record, is not visited again.
+template <typename T>
+__global__ void __launch_bounds__(64) k_rollout_cost(DevModel<T> m, RolloutBuf<T> w, CostBuf<T> c, int v0, int t) {
+  const int b = blockIdx.x, l = threadIdx.x;
+  int flags = 0;
+  if (l == 0) flags = (w.live[b] ? 1 : 0) | (w.warning[b] != 0 ? 2 : 0);
+  flags = __builtin_amdgcn_readfirstlane(flags);
+  if (!(flags & 1)) return;
+  const int v = v0 + b, env = v / w.K, nu = w.nu, nsd = w.nsd;
+  if (flags & 2) {
+    if (l == 0) {
+      const double inf = __builtin_huge_val();
+      c.cost[v] = inf;
+      if (c.terms) { c.terms[(size_t)v * 3] = inf; c.terms[(size_t)v * 3 + 1] = inf; c.terms[(size_t)v * 3 + 2] = inf; }
+    }
+    return;
+  }
+  const bool last = t + 1 == w.T_steps;
+  const double sx = cost_state_part(m, w, c, b, env, t + 1, last ? c.w_xf : c.w_x, l);
+  double su = 0, ss = 0;
+  if (c.w_u) {
+    const T* u = w.ctrl + (size_t)b * nu;  // still the control handed to step t
+    su = wave_half_wsq(c.w_u + (size_t)env * nu, nu, l, [&](int i) { return u[i]; });
+  }
+  const T* ws = last ? c.w_sf : c.w_s;
+  if (c.sgoal && ws && w.sens) {
+    const T* sd = w.sens + (size_t)b * nsd;
+    const T* sg = c.sgoal + ((size_t)env * c.sensor_rows + (c.sensor_rows == 1 ? 0 : t)) * nsd;
+    ss = wave_half_wsq(ws + (size_t)env * nsd, nsd, l, [&](int i) { return (T)(sd[i] - sg[i]); });
+  }
+  if (l == 0) {
+    c.cost[v] = c.cost[v] + ((sx + su) + ss);
+    if (c.terms) {
+      double* tr = c.terms + (size_t)v * 3;
+      tr[0] = tr[0] + sx; tr[1] = tr[1] + su; tr[2] = tr[2] + ss;
+    }
+  }
+}
+
 int rollout_dims(const mgx_model* m, RolloutDims* d) {
   mgx_model_info info;
   const int rc = mgx_model_get_info(m, &info);
@@ -171,7 +262,8 @@ int rollout_dims(const mgx_model* m, RolloutDims* d) {
 
 template <typename T>
 int run_rollout(const mgx_model* m, const DevModel<T>& M, const RolloutDims& d, const mgx_state* s, const mgx_rollout_io* io,
-                const mgx_feedback_io* fio, bool sensors, int n_env, const uint8_t* mask, hipStream_t st) {
+                const mgx_feedback_io* fio, const mgx_cost_io* cio, bool sensors, int n_env, const uint8_t* mask,
+                hipStream_t st) {
   const RolloutLayout o = rollout_layout(d, io->slots, sensors);
   char* ws = (char*)io->workspace;
   const int Tn = io->n_step, K = io->n_roll;
@@ -191,6 +283,13 @@ int run_rollout(const mgx_model* m, const DevModel<T>& M, const RolloutDims& d, 
     f.u_nom = (const T*)fio->u_nom; f.x_nom = (const T*)fio->x_nom; f.k_ff = (const T*)fio->k_ff;
     f.alpha = (const T*)fio->alpha; f.gain = (const T*)fio->gain; f.clamp = fio->flags & MGX_FEEDBACK_CLAMP ? 1 : 0;
   }
+  CostBuf<T> c{};
+  if (cio) {
+    c.goal = (const T*)cio->goal; c.w_x = (const T*)cio->w_x; c.w_xf = (const T*)cio->w_xf; c.w_u = (const T*)cio->w_u;
+    c.sgoal = (const T*)cio->sensor_goal; c.w_s = (const T*)cio->w_s; c.w_sf = (const T*)cio->w_sf;
+    c.goal_rows = cio->goal_rows; c.sensor_rows = cio->sensor_rows;
+    c.cost = (double*)cio->cost; c.terms = (double*)cio->terms;
+  }
   const size_t fb_lds = (size_t)(2 * d.nv > 0 ? 2 * d.nv : 1) * sizeof(double);
   mgx_state vs{};
   vs.qpos = w.qpos; vs.qvel = w.qvel; vs.qacc_warmstart = w.qacc; vs.ctrl = w.ctrl; vs.qfrc_applied = w.qfrc;
@@ -208,6 +307,10 @@ int run_rollout(const mgx_model* m, const DevModel<T>& M, const RolloutDims& d, 
     const int cnt = (int)(total - v0 < io->slots ? total - v0 : io->slots);
     hipLaunchKernelGGL(k_rollout_begin<T>, dim3(cnt), dim3(64), 0, st, *s, w, (int)v0, mask);
     MGX_HIPCHK(hipGetLastError());
+    if (cio) {
+      hipLaunchKernelGGL(k_rollout_cost_begin<T>, dim3(cnt), dim3(64), 0, st, M, w, c, (int)v0);
+      MGX_HIPCHK(hipGetLastError());
+    }
     for (int t = 0; t < Tn; t++) {
       // the library's own step, exactly as a caller of mgx_step gets it; rollouts of deselected
       // envs hold no state, and diverged ones are done: both are masked out by the live flags
@@ -225,6 +328,11 @@ int run_rollout(const mgx_model* m, const DevModel<T>& M, const RolloutDims& d, 
         }
         rc = mgx_sensor(m, &vs, need_fwd ? &fo : nullptr, ws + o.sens, cnt, w.live, st);
         if (rc) return rc;
+      }
+      if (cio) {
+        // u_t, x_(t+1) and its sensors are in the workspace now; record overwrites ctrl and live
+        hipLaunchKernelGGL(k_rollout_cost<T>, dim3(cnt), dim3(64), 0, st, M, w, c, (int)v0, t);
+        MGX_HIPCHK(hipGetLastError());
       }
       hipLaunchKernelGGL(k_rollout_record<T>, dim3(cnt), dim3(64), 0, st, w, (int)v0, t);
       MGX_HIPCHK(hipGetLastError());
@@ -249,9 +357,10 @@ int64_t mgx_rollout_bytes(const mgx_model* m, int slots, int with_sensors) {
 
 namespace {
 
-// mgx_rollout, and mgx_rollout_feedback with its checked mgx_feedback_io
-int rollout_call(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fio, int n_env,
-                 const uint8_t* env_mask, void* stream) {
+// mgx_rollout, mgx_rollout_feedback with its checked mgx_feedback_io, and mgx_rollout_cost with its
+// checked mgx_cost_io on top of either
+int rollout_call(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fio,
+                 const mgx_cost_io* cio, int n_env, const uint8_t* env_mask, void* stream) {
   if (!m || !io || n_env < 0) return host_fail(MGX_E_ARG, "null argument or n_env < 0");
   int rc = host_check_state(s);
   if (rc) return rc;
@@ -261,7 +370,8 @@ int rollout_call(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* i
   if (io->slots < 1) return host_fail(MGX_E_ARG, "slots must be >= 1");
   if ((int64_t)n_env * io->n_roll > INT32_MAX) return host_fail(MGX_E_ARG, "n_env * n_roll exceeds 2^31 - 1");
   bool sensors = false;
-  if (io->sensordata) {
+  const bool want_sensors = io->sensordata || (cio && cio->sensor_goal);  // a sensor term needs the staging rows
+  if (want_sensors) {
     // what mgx_forward and mgx_sensor would refuse, before anything is launched
     if (m->wide) return host_fail(MGX_E_UNSUPPORTED, std::string("mgx_forward: ") + MGX_WIDE_MSG);
     if ((m->precision == MGX_F32 ? m->mf.cone : m->md.cone) != 0)
@@ -273,13 +383,13 @@ int rollout_call(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* i
   RolloutDims d;
   rc = rollout_dims(m, &d);
   if (rc) return rc;
-  if (!io->workspace || io->workspace_bytes < rollout_layout(d, io->slots, io->sensordata != nullptr).bytes)
+  if (!io->workspace || io->workspace_bytes < rollout_layout(d, io->slots, want_sensors).bytes)
     return host_fail(MGX_E_ARG, "workspace smaller than mgx_rollout_bytes");
   const bool records = fio && (fio->ctrl_out || fio->warm_out);
-  if (n_env == 0 || (!io->state && !sensors && !io->n_done && !records)) return MGX_OK;
+  if (n_env == 0 || (!io->state && !(sensors && io->sensordata) && !io->n_done && !records && !cio)) return MGX_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (m->precision == MGX_F32) return run_rollout<float>(m, m->mf, d, s, io, fio, sensors, n_env, env_mask, st);
-  return run_rollout<double>(m, m->md, d, s, io, fio, sensors, n_env, env_mask, st);
+  if (m->precision == MGX_F32) return run_rollout<float>(m, m->mf, d, s, io, fio, cio, sensors, n_env, env_mask, st);
+  return run_rollout<double>(m, m->md, d, s, io, fio, cio, sensors, n_env, env_mask, st);
 }
 
 }  // namespace
@@ -288,13 +398,16 @@ extern "C" {
 
 int mgx_rollout(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, int n_env, const uint8_t* env_mask,
                 void* stream) {
-  return rollout_call(m, s, io, nullptr, n_env, env_mask, stream);
+  return rollout_call(m, s, io, nullptr, nullptr, n_env, env_mask, stream);
 }
+
+}  // extern "C"
+
+namespace {
 
 // The checks that concern the feedback law read io and fb only and come first, so a caller's
 // mistake in them is named whatever the model and the state are.
-int mgx_rollout_feedback(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fb,
-                         int n_env, const uint8_t* env_mask, void* stream) {
+int feedback_check(const mgx_rollout_io* io, const mgx_feedback_io* fb) {
   if (!io) return host_fail(MGX_E_ARG, "null mgx_rollout_io");
   if (!fb || !fb->u_nom) return host_fail(MGX_E_ARG, "mgx_rollout_feedback needs an mgx_feedback_io with u_nom");
   if (io->hold != 1) return host_fail(MGX_E_ARG, "mgx_rollout_feedback: hold must be 1");
@@ -302,7 +415,37 @@ int mgx_rollout_feedback(const mgx_model* m, const mgx_state* s, const mgx_rollo
     return host_fail(MGX_E_ARG, "mgx_rollout_feedback: io->ctrl must be NULL and MGX_ROLLOUT_SHARED_CTRL unset (the nominal control is fb->u_nom)");
   if (fb->gain && !fb->x_nom) return host_fail(MGX_E_ARG, "mgx_feedback_io.gain needs x_nom");
   if (fb->flags & ~MGX_FEEDBACK_CLAMP) return host_fail(MGX_E_ARG, "unknown mgx_feedback_io.flags bits");
-  return rollout_call(m, s, io, fb, n_env, env_mask, stream);
+  return MGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgx_rollout_feedback(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fb,
+                         int n_env, const uint8_t* env_mask, void* stream) {
+  const int rc = feedback_check(io, fb);
+  if (rc) return rc;
+  return rollout_call(m, s, io, fb, nullptr, n_env, env_mask, stream);
+}
+
+// The checks of the cost read io and cost only and come first, then those of the feedback law.
+int mgx_rollout_cost(const mgx_model* m, const mgx_state* s, const mgx_rollout_io* io, const mgx_feedback_io* fb,
+                     const mgx_cost_io* cost, int n_env, const uint8_t* env_mask, void* stream) {
+  if (!io) return host_fail(MGX_E_ARG, "null mgx_rollout_io");
+  if (!cost || !cost->cost) return host_fail(MGX_E_ARG, "mgx_rollout_cost needs an mgx_cost_io with cost");
+  if (cost->goal && cost->goal_rows != 1 && cost->goal_rows != (int64_t)io->n_step + 1)
+    return host_fail(MGX_E_ARG, "mgx_cost_io.goal_rows must be 1 or n_step + 1");
+  if (cost->sensor_goal && cost->sensor_rows != 1 && cost->sensor_rows != io->n_step)
+    return host_fail(MGX_E_ARG, "mgx_cost_io.sensor_rows must be 1 or n_step");
+  if ((cost->w_s || cost->w_sf) && !cost->sensor_goal) return host_fail(MGX_E_ARG, "mgx_cost_io.w_s / w_sf need sensor_goal");
+  if ((cost->w_x || cost->w_xf) && !cost->goal) return host_fail(MGX_E_ARG, "mgx_cost_io.w_x / w_xf need goal");
+  if (cost->flags) return host_fail(MGX_E_ARG, "unknown mgx_cost_io.flags bits");
+  if (fb) {
+    const int rc = feedback_check(io, fb);
+    if (rc) return rc;
+  }
+  return rollout_call(m, s, io, fb, cost, n_env, env_mask, stream);
 }
 
 }  // extern "C"

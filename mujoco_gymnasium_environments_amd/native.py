@@ -206,6 +206,8 @@ _SIGS = {
     "mgx_state_integrate": ([_VP, _VP, _VP, _VP, C.c_int64, _VP], C.c_int),
     "mgx_rollout_feedback": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxRolloutIO),
                               C.POINTER(cabi.MgxFeedbackIO), C.c_int, _VP, _VP], C.c_int),
+    "mgx_rollout_cost": ([_VP, C.POINTER(cabi.MgxState), C.POINTER(cabi.MgxRolloutIO), C.POINTER(cabi.MgxFeedbackIO),
+                          C.POINTER(cabi.MgxCostIO), C.c_int, _VP, _VP], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 

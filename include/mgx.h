@@ -1347,6 +1347,67 @@ int mgx_render_camera(const mgx_model *m, const void *scene, int cam, int height
                       const uint8_t *geom_enable, int bodyexclude, uint8_t *rgb8, float *rgbf, float *depth,
                       int32_t *seg, int n_env, const uint8_t *env_mask, void *stream);
 
+/* ---- LQR backward pass (the Riccati recursion of iLQR, optionally box-constrained) ------------- */
+/* The time-varying LQR backward pass of ilqr.lqr_backward for every env in one kernel, in the
+ * model's real type T; the model supplies only the precision and the device, n (the tangent-state
+ * width, 2nv of a model, but any 1 <= n <= 4096), m (controls, 1 <= m <= MGX_LQR_MAX_CTRL) and
+ * T >= 1 are free. All arrays are row-major. With V_x = Vx_T, V_xx = Vxx_T, for t = T-1 .. 0:
+ *   Q_u  = l_u + B' V_x;   Q_ux = l_ux + B' V_xx A;   Q_uu = l_uu + diag(luu_diag) + B' V_xx B;
+ *   H    = Q_uu + mu max(1, tr Q_uu / m) I          (the gains only; its lower triangle is read);
+ *   plain:  k = -H^-1 Q_u, K = -H^-1 Q_ux by Cholesky H = L L';
+ *   MGX_LQR_BOX:  k = argmin 1/2 k' H k + Q_u' k over lo_t <= k <= hi_t by projected Newton
+ *     (Tassa, Mansard, Todorov 2014), from x = clamp(k_(t+1), lo_t, hi_t) (zero at t = T-1):
+ *       g = Q_u + H x; control i is clamped when (x_i = lo_i and g_i > 0) or (x_i = hi_i and
+ *       g_i < 0), free otherwise. Stop when no control is free, or when the free set is the one
+ *       of the previous iteration and that iteration took the full step without touching a bound.
+ *       Cholesky of H's free block (again only when the set changed); y = the minimiser over the
+ *       free controls with the clamped ones held, d = y - x on the free controls, 0 elsewhere;
+ *       stop when d'g >= 0. Armijo: step = 1, 0.6, 0.6^2, ... (at most 60): x+ = clamp(x + step d)
+ *       (y itself at step 1), dx = x+ - x, accepted when dx'g < 0 and dx'g + 1/2 dx' H dx <=
+ *       0.1 dx'g: the decrease of the quadratic against the first-order decrease along the
+ *       projected step (Bertsekas 1982), which for a step inside the box is step d'g.
+ *     At most 100 iterations. K = -(H_ff)^-1 (Q_ux)_f on the free rows, 0 on the clamped rows;
+ *   expected += (k' Q_u, 1/2 k' Q_uu k)            (the unregularised Q_uu);
+ *   the cost-to-go of the policy du = k + K dx, a sum of congruences, with Acl = A + B K:
+ *   V_x  <- l_x + K' (l_u + l_uu k) + l_ux' k + Acl' (V_x + V_xx B k);
+ *   V_xx <- l_xx + diag(lxx_diag) + K' l_uu K + K' l_ux + l_ux' K + Acl' V_xx Acl;
+ *   V_xx <- (V_xx + V_xx') / 2.
+ * (l_uu in the V updates includes diag(luu_diag).) Every sum runs in a fixed order: two calls give
+ * the same bits. info bit 0: a pivot that is not positive and finite; the env's pass ends there and
+ * its outputs are meaningless (rows of later steps keep what they held). Bit 1: a QP reached its
+ * iteration cap or its line search found no step; k is then the last iterate (feasible).
+ * Asynchronous on the stream; no allocation, no synchronisation, capturable; one workgroup per env,
+ * nothing crosses workgroups. Outputs of envs that env_mask deselects are left untouched.
+ * Not provided: state constraints, constraints coupling controls, costs other than the quadratic
+ * terms above. */
+#define MGX_LQR_MAX_CTRL 64
+#define MGX_LQR_BOX 1        /* flags: lo / hi are given */
+
+typedef struct mgx_lqr_io {
+  int32_t n, m, T;           /* n = tangent-state width, m = controls, T = steps */
+  int32_t flags;             /* MGX_LQR_* bits */
+  const void *A, *B;         /* in  [N][T][n][n], [N][T][n][m] */
+  const void *lx, *lxx, *lu, *luu, *lux;  /* in  [N][T][n], [..][n][n], [..][m], [..][m][m], [..][m][n];
+                                             lxx / luu / lux nullable = zero */
+  const void *lxx_diag, *luu_diag;        /* in  [N][T][n], [N][T][m], nullable: added to the diagonal */
+  const void *Vx_T, *Vxx_T;  /* in  [N][n], [N][n][n] */
+  const void *mu;            /* in  [N] */
+  const void *lo, *hi;       /* in  [N][T][m]: bounds on du_t (ctrl limit minus nominal); +-inf = none */
+  void *k_ff, *gain, *expected;           /* out [N][T][m], [N][T][m][n], [N][2] */
+  uint8_t *free_set;         /* out [N][T][m], nullable: 1 = the control is free in the QP's solution */
+  int32_t *info;             /* out [N] */
+  void *workspace;           /* mgx_lqr_backward_bytes(m, n, m, n_env) bytes, 16-byte aligned */
+  uint64_t workspace_bytes;
+} mgx_lqr_io;
+
+/* The workspace of one call: per env three n x n matrices, two n x m, one m x m and two n-vectors
+ * of T. MGX_E_ARG (negative) for sizes out of range. */
+int64_t mgx_lqr_backward_bytes(const mgx_model *m, int n, int m_ctrl, int n_env);
+/* MGX_E_ARG for n, m or T out of range, unknown flag bits, MGX_LQR_BOX without lo and hi, a
+ * workspace smaller than mgx_lqr_backward_bytes, n_env < 0, or a NULL model, io, A, B, lx, lu,
+ * Vx_T, Vxx_T, mu, k_ff, gain, expected or info. */
+int mgx_lqr_backward(const mgx_model *m, const mgx_lqr_io *io, int n_env, const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -359,6 +359,18 @@ class MgxCostIO(C.Structure):  # include/mgx.h mgx_cost_io (mgx_rollout_cost)
                 ("terms", C.c_void_p)]
 
 
+MGX_LQR_MAX_CTRL = 64  # include/mgx.h: controls of one mgx_lqr_backward problem
+MGX_LQR_BOX = 1  # mgx_lqr_io.flags
+
+
+class MgxLqrIO(C.Structure):  # include/mgx.h mgx_lqr_io (mgx_lqr_backward)
+    _fields_ = [(n, C.c_int32) for n in ["n", "m", "T", "flags"]] + \
+               [(n, C.c_void_p) for n in ["A", "B", "lx", "lxx", "lu", "luu", "lux", "lxx_diag", "luu_diag", "Vx_T",
+                                          "Vxx_T", "mu", "lo", "hi", "k_ff", "gain", "expected", "free_set", "info",
+                                          "workspace"]] + \
+               [("workspace_bytes", C.c_uint64)]
+
+
 MGX_RENDER_MAX_LAYERS, MGX_RENDER_MAX_LIGHT = 4, 8  # include/mgx.h
 MGX_TEX_2D, MGX_TEX_CUBE, MGX_TEX_SKYBOX = 0, 1, 2  # mjcf.TEX_TYPES
 MGX_BUILTIN_NONE, MGX_BUILTIN_GRADIENT, MGX_BUILTIN_CHECKER, MGX_BUILTIN_FLAT = 0, 1, 2, 3  # mjcf.TEX_BUILTIN

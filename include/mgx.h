@@ -1408,6 +1408,58 @@ int64_t mgx_lqr_backward_bytes(const mgx_model *m, int n, int m_ctrl, int n_env)
  * Vx_T, Vxx_T, mu, k_ff, gain, expected or info. */
 int mgx_lqr_backward(const mgx_model *m, const mgx_lqr_io *io, int n_env, const uint8_t *env_mask, void *stream);
 
+/* ---- Kalman covariance step (predict and / or Joseph-form measurement update) ------------------ */
+/* The covariance part of one (extended) Kalman filter step, estimation.kalman_step, for every env
+ * in one kernel, in the model's real type T; the model supplies only the precision and the device,
+ * n (the tangent-state width, 2nv of a model, but any 1 <= n <= 4096) and p (measurement rows,
+ * 1 <= p <= MGX_EKF_MAX_MEAS; with MGX_EKF_PREDICT alone p only sizes the workspace: pass 1) are
+ * free. All arrays are row-major. flags: MGX_EKF_PREDICT, MGX_EKF_UPDATE or both (predict first).
+ *   MGX_EKF_PREDICT (A given):
+ *     P <- A P A' + Q + diag(Q_diag)   (Q, Q_diag nullable = zero);   P <- (P + P') / 2.
+ *   MGX_EKF_UPDATE (H, R_diag, resid given), r = resid = z - h(x^):
+ *     a row i with row_mask[i] = 0 (not measured) has its row of H, r_i and R_i set to zero and its
+ *     row and column of S set to the identity's, so it adds nothing to any output and needs no
+ *     index compaction (the clamped controls of the LQR backward pass are handled the same way);
+ *     G = P H';   S = H G + diag(R);   S = L L' (Cholesky);   K = G S^-1;   dx = K r;
+ *     F = I - K H;   P <- F P F' + K diag(R) K'   (Joseph form);   P <- (P + P') / 2;
+ *     nis = (r' S^-1 r, log det S) = (y' y, 2 sum log L_ii) with y = L^-1 r, over the measured rows.
+ * Why the Joseph form: it is a sum of two congruences of positive semidefinite matrices, so P stays
+ * positive semidefinite whatever rounding does to K; P - K S K' subtracts two matrices of the size
+ * of P and in fp32 loses positive definiteness where the measurement is informative.
+ * info bit 0: a pivot of S is not positive and finite (R_diag must be > 0). That env's update is
+ * skipped: P keeps the predicted covariance (with MGX_EKF_UPDATE alone: the P given), dx = 0,
+ * gain = 0, nis = NaN. With every row masked dx is exactly 0 and P is its symmetric part.
+ * Every sum runs in a fixed order: two calls give the same bits. Asynchronous on the stream; no
+ * allocation, no synchronisation, capturable; one workgroup per env, nothing crosses workgroups.
+ * Outputs of envs that env_mask deselects, P included, are left untouched. MGX_EKF_PREDICT alone
+ * writes P and info only.
+ * Not provided: a full (non-diagonal) R, a square-root or UD form, smoothing. */
+#define MGX_EKF_MAX_MEAS 64
+#define MGX_EKF_PREDICT 1    /* flags: A (and Q, Q_diag) are given */
+#define MGX_EKF_UPDATE 2     /* flags: H, R_diag and resid are given */
+
+typedef struct mgx_ekf_io {
+  int32_t n, p;              /* n = tangent-state width, p = measurement rows */
+  int32_t flags;             /* MGX_EKF_* bits */
+  int32_t reserved;          /* 0 */
+  const void *A, *Q, *Q_diag;         /* in  [N][n][n], [N][n][n] nullable, [N][n] nullable */
+  const void *H, *R_diag, *resid;     /* in  [N][p][n], [N][p] (> 0), [N][p] */
+  const uint8_t *row_mask;   /* in  [N][p], nullable: 0 = the row is not measured */
+  void *P;                   /* io  [N][n][n], in place */
+  void *dx, *gain, *nis;     /* out [N][n], [N][n][p] nullable, [N][2] */
+  int32_t *info;             /* out [N] */
+  void *workspace;           /* mgx_ekf_bytes(m, n, p, n_env) bytes, 16-byte aligned */
+  uint64_t workspace_bytes;
+} mgx_ekf_io;
+
+/* The workspace of one call: per env two n x n matrices, three n x p and one p x p of T.
+ * MGX_E_ARG (negative) for sizes out of range. */
+int64_t mgx_ekf_bytes(const mgx_model *m, int n, int p, int n_env);
+/* MGX_E_ARG for n or p out of range, no flag or unknown flag bits, MGX_EKF_PREDICT without A,
+ * MGX_EKF_UPDATE without H, R_diag, resid, dx or nis, a workspace smaller than mgx_ekf_bytes,
+ * n_env < 0, or a NULL model, io, P or info. */
+int mgx_ekf_step(const mgx_model *m, const mgx_ekf_io *io, int n_env, const uint8_t *env_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .dynamics import DynamicsMethods
 from .ik import IkMethods
 from .ilqr import IlqrMethods
 from .sampling import SamplingMethods
+from .estimation import EstimationMethods
 from .rays import RayMethods
 from .render import RenderMethods
 from .sensors import SensorMethods
@@ -68,7 +69,7 @@ class NativeModel:
 
 
 class PhysicsBatch(RayMethods, RenderMethods, SensorMethods, DynamicsMethods, IkMethods, TransitionMethods, RolloutMethods,
-                   ManifoldMethods, IlqrMethods, SensorFdMethods, SamplingMethods):
+                   ManifoldMethods, IlqrMethods, SensorFdMethods, SamplingMethods, EstimationMethods):
     def __init__(self, model: mjcf.Model, n_env: int, precision: str = "f64", device: str = "cuda:0",
                  native: Optional[NativeModel] = None):
         self.model = model

@@ -371,6 +371,17 @@ class MgxLqrIO(C.Structure):  # include/mgx.h mgx_lqr_io (mgx_lqr_backward)
                [("workspace_bytes", C.c_uint64)]
 
 
+MGX_EKF_MAX_MEAS = 64  # include/mgx.h: measurement rows of one mgx_ekf_step problem
+MGX_EKF_PREDICT, MGX_EKF_UPDATE = 1, 2  # mgx_ekf_io.flags
+
+
+class MgxEkfIO(C.Structure):  # include/mgx.h mgx_ekf_io (mgx_ekf_step)
+    _fields_ = [(n, C.c_int32) for n in ["n", "p", "flags", "reserved"]] + \
+               [(n, C.c_void_p) for n in ["A", "Q", "Q_diag", "H", "R_diag", "resid", "row_mask", "P", "dx", "gain",
+                                          "nis", "info", "workspace"]] + \
+               [("workspace_bytes", C.c_uint64)]
+
+
 MGX_RENDER_MAX_LAYERS, MGX_RENDER_MAX_LIGHT = 4, 8  # include/mgx.h
 MGX_TEX_2D, MGX_TEX_CUBE, MGX_TEX_SKYBOX = 0, 1, 2  # mjcf.TEX_TYPES
 MGX_BUILTIN_NONE, MGX_BUILTIN_GRADIENT, MGX_BUILTIN_CHECKER, MGX_BUILTIN_FLAT = 0, 1, 2, 3  # mjcf.TEX_BUILTIN

@@ -21,6 +21,7 @@ from ..dynamics import DynamicsForwarding
 from ..ik import IkForwarding
 from ..ilqr import IlqrForwarding
 from ..sampling import SamplingForwarding
+from ..estimation import EstimationForwarding
 from ..native import NativeError, check, lib
 from ..rays import RayForwarding
 from ..render import RenderForwarding, env_frame
@@ -44,7 +45,8 @@ def device_actions(actions: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 class TaskVectorEnv(RayForwarding, RenderForwarding, SensorForwarding, DynamicsForwarding, IkForwarding, TransitionForwarding,
-                    RolloutForwarding, ManifoldForwarding, IlqrForwarding, SensorFdForwarding, SamplingForwarding):
+                    RolloutForwarding, ManifoldForwarding, IlqrForwarding, SensorFdForwarding, SamplingForwarding,
+                    EstimationForwarding):
     """``num_envs`` envs of one task stepping in lockstep on one GPU, one fused launch (or one
     staged pipeline) per env step, with same-step autoreset."""
 

@@ -344,6 +344,10 @@ class StreamShardedEnv:
                                    stream=cs, only=only, out=full.rows(a, b), **kw)
         return RolloutResult(**{f: getattr(full, f) for f in ROLLOUT_OUTPUTS if getattr(part, f) is not None})
 
+    def ekf(self, *args, **kw):
+        """Not provided on sharded envs: the filter keeps one belief batch for one PhysicsBatch."""
+        raise NotImplementedError("ekf is not provided on StreamSharded*Env: build the filter on one shard's env or batch")
+
     def info(self) -> Dict[str, Any]:
         return _CatInfo(self.shards)
 

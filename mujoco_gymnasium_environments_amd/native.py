@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["mgx_api.hip", "mgx_staged_host.hip", "mgx_soccer.hip", "mgx_pgs.hip", "mgx_rk_staged.hip", "mgx_pk_staged.hip",
            "mgx_step.hip", "mgx_parkour.hip", "mgx_bipedal.hip", "mgx_dancing.hip",
            "mgx_martial.hip", "mgx_assembly.hip", "mgx_construction.hip", "mgx_ray.hip", "mgx_sensor.hip", "mgx_dyn.hip", "mgx_fd.hip",
-           "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip", "mgx_manifold.hip", "mgx_lqr.hip"]
+           "mgx_rollout.hip", "mgx_render.hip", "mgx_ik.hip", "mgx_manifold.hip", "mgx_lqr.hip", "mgx_ekf.hip"]
 # per-translation-unit flags: the staged solver's FMA chains must not be SLP-packed (mgx_pgs.hip)
 SOURCE_FLAGS = {"mgx_pgs.hip": ["-fno-slp-vectorize"], "mgx_rk_staged.hip": ["-fno-slp-vectorize"],
                 "mgx_pk_staged.hip": ["-fno-slp-vectorize"]}
@@ -32,7 +32,7 @@ TU_HEADERS = {"mgx_assembly.hip": ["mgx_assembly.h"], "mgx_sensor.hip": ["mgx_se
               "mgx_ik.hip": ["mgx_ik.h", "mgx_dyn.h"],
               "mgx_fd.hip": ["mgx_fd.h", "mgx_manifold.h", "mgx_sensor.h"],
               "mgx_rollout.hip": ["mgx_rollout.h", "mgx_sensor.h", "mgx_manifold.h"], "mgx_manifold.hip": ["mgx_manifold.h"],
-              "mgx_render.hip": ["mgx_render.h"], "mgx_lqr.hip": ["mgx_lqr.h"]}
+              "mgx_render.hip": ["mgx_render.h"], "mgx_lqr.hip": ["mgx_lqr.h"], "mgx_ekf.hip": ["mgx_ekf.h"]}
 
 MGX_OK = 0
 MGX_F32 = 0
@@ -210,6 +210,8 @@ _SIGS = {
                           C.POINTER(cabi.MgxCostIO), C.c_int, _VP, _VP], C.c_int),
     "mgx_lqr_backward_bytes": ([_VP, C.c_int, C.c_int, C.c_int], C.c_int64),
     "mgx_lqr_backward": ([_VP, C.POINTER(cabi.MgxLqrIO), C.c_int, _VP, _VP], C.c_int),
+    "mgx_ekf_bytes": ([_VP, C.c_int, C.c_int, C.c_int], C.c_int64),
+    "mgx_ekf_step": ([_VP, C.POINTER(cabi.MgxEkfIO), C.c_int, _VP, _VP], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
